@@ -1,16 +1,25 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: Gkeys/s of the MI355X-native LSD radix sort.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one full sort of one batch of synthetic keys that is already resident
 in HBM when the timed region starts -- whatever route the library takes for it
 (`config.passes` names it from rsx_info.hybrid).  For the N = 1 workload that is,
 since round 3: a sample kernel that proves the input unsorted and every column kept,
 two MSB scatter passes into per-bucket slots (the second writes two bytes per key)
-and the leaves; the same run then times the reference's own loop --
-histogram + one pass per kept column, radix_sort.hpp:82-90 -- for comparison
-(`kernels.lsd_only_*`, never `value`).
+and the leaves.
+
+A plain run sets up, warms up, times the K steps and prints the result line.  With
+--full it also checks the last step's output (sorted, and the same keys as its input),
+times the reference's own loop -- histogram + one pass per kept column,
+radix_sort.hpp:82-90 -- for comparison (`kernels.lsd_only_*`, never `value`) and,
+at N = 1, the CPU baseline (`cpu_baseline`).
+
+--dump-outputs DIR writes what the last timed step returned, right after the timed
+steps: DIR/sorted_keys.npy, the sorted u32 keys as float64 (exact), all of them up to
+2^22 keys, else the keys at 2^22 fixed positions (seeded, ascending), 32 MiB.  At N > 1
+it is rank 0's part of the global order.
 
   N = 1   BASELINE.json configs[1]: 2^28 uniform-random u32 keys (splitmix64,
           seed 1 for the first batch), 4 kept 8-bit columns, keys only.
@@ -20,10 +29,11 @@ histogram + one pass per kept column, radix_sort.hpp:82-90 -- for comparison
           (radix_sorting_amd/multi.py); launched by torch.distributed.run, one
           rank per GPU.  Weak scaling: per-GPU work is fixed as N grows.
 
-Every step sorts a different, still-unsorted batch (K + W batches are generated
-on the device up front: at 1 GiB each they fit easily in 288 GB), so no step
-takes the reference's pre-sorted early exit and nothing is copied inside the
-timed region.
+Every step sorts a different, still-unsorted batch (batch b is splitmix64 seed 1 + b,
+generated on the device), so no step takes the reference's pre-sorted early exit and
+nothing is copied inside the timed region.  Up to POOL_BYTES of batches are generated
+up front (K + W = 23 batches of 1 GiB by default: all of them); a longer run refills the
+pool between stretches of timed steps, outside the timed region, and sums the stretches.
 
 The one JSON line printed by rank 0 carries, besides the contract's fields,
   roofline      the kernel with the LARGEST time per step (the library times its kernels by
@@ -34,7 +44,7 @@ The one JSON line printed by rank 0 carries, besides the contract's fields,
                 the sum of their algorithmic bytes over the step time; `traffic` = the
                 dominant kernel's HBM bytes per launch from the committed rocprofv3 --pmc
                 passes (profiles/pmc_kernels.json, which names the commit it was measured at);
-  cpu_baseline  the real reference (oracle/_ref/libref*.so, kind "reference") or, when
+  cpu_baseline  (--full) the real reference (oracle/_ref/libref*.so, kind "reference") or, when
                 that is absent, the C restatement (kind "port"), timed on ONE pinned host core
                 on the whole 2^28-key batch 0 (median of 5) and on 40 M keys (single shot),
                 CPU model and core count beside it.  N = 1, rank 0 only.
@@ -55,6 +65,9 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 HBM_PEAK_GBS = 8000.0   # MI355X_MICROARCH.md: 8 TB/s HBM3E spec peak
+POOL_BYTES = 32 << 30   # device memory for the steps' input batches (a longer run refills them between stretches)
+DUMP_SAMPLE = 1 << 22   # --dump-outputs: keys written (float64: 32 MiB)
+DUMP_SEED = 20261016
 
 
 def load_baseline_metric():
@@ -187,6 +200,20 @@ def cpu_baseline(log2n=28, reps=5):
                       "core %s of %d (%s)" % (log2n, reps, t_full * 1e3, t_40m * 1e3, pinned, os.cpu_count(), cpu_model())}
 
 
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the sorted u32 keys of the last timed step (an int32 device tensor holding their bits) as float64 -- all
+    of them, or DUMP_SAMPLE of them at fixed seeded positions, ascending -- to out_dir/sorted_keys.npy."""
+    import numpy as np
+    import torch
+    n = res.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE, dtype=np.int64))
+        res = res.index_select(0, torch.from_numpy(idx).to(res.device))
+    keys = res.cpu().numpy().view(np.uint32).astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "sorted_keys.npy"), keys)
+
+
 def launch_ranks(args_list, gpus, script=None):
     """`python bench.py --gpus N` without a launcher: this process stays free of the GPU, starts the N ranks as
     `python -m torch.distributed.run ... bench.py <same arguments>`, relays their output and ends with rank 0's JSON line
@@ -275,10 +302,16 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--log2n", type=int, default=None, help="keys per GPU (default 28 at N=1, 29 at N>1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also check the last step's output, time the one-pass-per-column loop and (N = 1) the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sorted keys (or a fixed sample of them) to DIR/sorted_keys.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--force-exchange", action="store_true",
                     help="test switch: take the N>1 code path (process group, MSD split, all-to-all-v) whatever N is")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(sys.argv[1:], args.gpus)     # (before anything touches the GPU; does not return)
 
@@ -308,14 +341,12 @@ def main():
     log2n = args.log2n if args.log2n is not None else (29 if sharded else 28)
     n = 1 << log2n
     dev = torch.device("cuda", local_rank)
-    nbatches = K + W
     # distinct unsorted batch per step; batch b of rank r continues the splitmix stream of seed 1 + b
-    # at global index r * n, so the N-rank job sorts exactly the sequence one rank would generate
-    batches = []
-    for b in range(nbatches):
-        t = torch.empty(n, dtype=torch.int32, device=dev)
-        rsa.fill_splitmix(t, seed=1 + b, first_index=rank * n)
-        batches.append(t)
+    # at global index r * n, so the N-rank job sorts exactly the sequence one rank would generate.  Batch b lives in
+    # batches[b % pool]; `filled` is the first batch not generated yet
+    pool = max(1, min(K + W, POOL_BYTES // (4 * n)))
+    batches = [torch.empty(n, dtype=torch.int32, device=dev) for _ in range(pool)]
+    filled = 0
     engine = multi.HipEngine(rsa.U32)
     engine.host_marks = {}
     cap = n + n // 4 if sharded else n
@@ -326,8 +357,8 @@ def main():
 
     def step(i):
         if not sharded:
-            return rsa.radix_sort(batches[i], scratch["aux"], dtype=rsa.U32)
-        return multi.distributed_sort(batches[i], engine, scratch=scratch, force_exchange=args.force_exchange)
+            return rsa.radix_sort(batches[i % pool], scratch["aux"], dtype=rsa.U32)
+        return multi.distributed_sort(batches[i % pool], engine, scratch=scratch, force_exchange=args.force_exchange)
 
     def fence():
         torch.cuda.synchronize()
@@ -339,41 +370,67 @@ def main():
         """order-independent sums of a batch (wrap-around int64): the keys' sum and the sum of key * (key >> 7)"""
         return torch.stack([t.sum(dtype=torch.int64), (t * (t >> 7)).sum(dtype=torch.int64)])
 
-    # (the last step's input, summed before anything sorts it: its output must be the same keys -- a sorted array of OTHER keys
-    # passes a sortedness test, and round 5's one-rank forced exchange of 2^31 bytes delivered just that)
-    sums_in = checksums(batches[W + K - 1])
+    sums_in = None
+
+    def generate(hi):
+        """batches filled .. hi - 1 into their slots (whose earlier batches have been sorted and fenced)"""
+        nonlocal filled, sums_in
+        for b in range(filled, hi):
+            rsa.fill_splitmix(batches[b % pool], seed=1 + b, first_index=rank * n)
+            if args.full and b == W + K - 1:
+                # (--full: the last step's input, summed before anything sorts it: its output must be the same keys -- a sorted
+                # array of OTHER keys passes a sortedness test, and round 5's one-rank forced exchange of 2^31 bytes delivered
+                # just that)
+                sums_in = checksums(batches[b % pool])
+        filled = hi
+
+    generate(pool)
     for i in range(W):
+        if i == filled:
+            fence()
+            generate(min(W + K, i + pool))
         step(i)
     fence()
     rsa.profile_begin()
-    t0 = time.perf_counter()
+    elapsed = 0.0
     last = None
-    for i in range(W, W + K):
-        last = step(i)
-    fence()
-    elapsed = time.perf_counter() - t0
+    i = W
+    while i < W + K:                  # (one stretch of timed steps per fill of the pool: a single one unless K + W > pool)
+        if i == filled:
+            generate(min(W + K, i + pool))
+            fence()
+        t0 = time.perf_counter()
+        while i < filled:
+            last = step(i)
+            i += 1
+        fence()
+        elapsed += time.perf_counter() - t0
     prof = rsa.profile_end()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(last[0], args.dump_outputs)
 
     if sharded:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    # sanity: the last step's output is sorted (unsigned order == signed order of bits ^ 0x80000000)
-    res = last[0]
-    flipped = res ^ torch.tensor(-2 ** 31, dtype=torch.int32, device=dev)
-    ok = bool((flipped[1:] >= flipped[:-1]).all().item()) if res.numel() > 1 else True
-    sums_out = checksums(res)
-    if sharded:
-        okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
-        dist.all_reduce(okt, op=dist.ReduceOp.MIN)
-        ok = bool(okt.item())
-        dist.all_reduce(sums_in, op=dist.ReduceOp.SUM)      # (int64, wrap-around: the ranks' keys move between ranks)
-        dist.all_reduce(sums_out, op=dist.ReduceOp.SUM)
-    if not ok:
-        raise SystemExit("bench: output of the last step is not sorted")
-    if not bool((sums_in == sums_out).all().item()):
-        raise SystemExit("bench: the output of the last step is sorted but does not hold the input's keys (checksums differ)")
+    ok = None
+    if args.full:
+        # sanity: the last step's output is sorted (unsigned order == signed order of bits ^ 0x80000000)
+        res = last[0]
+        flipped = res ^ torch.tensor(-2 ** 31, dtype=torch.int32, device=dev)
+        ok = bool((flipped[1:] >= flipped[:-1]).all().item()) if res.numel() > 1 else True
+        sums_out = checksums(res)
+        if sharded:
+            okt = torch.tensor([1 if ok else 0], dtype=torch.int32, device=dev)
+            dist.all_reduce(okt, op=dist.ReduceOp.MIN)
+            ok = bool(okt.item())
+            dist.all_reduce(sums_in, op=dist.ReduceOp.SUM)      # (int64, wrap-around: the ranks' keys move between ranks)
+            dist.all_reduce(sums_out, op=dist.ReduceOp.SUM)
+        if not ok:
+            raise SystemExit("bench: output of the last step is not sorted")
+        if not bool((sums_in == sums_out).all().item()):
+            raise SystemExit("bench: the output of the last step is sorted but does not hold the input's keys (checksums differ)")
     # per-phase GPU time of the LAST step, max over ranks (split / exchange / sort; the chunk pipeline overlaps the last two):
     # a first run on several GPUs should explain itself
     phase_max = None
@@ -396,11 +453,11 @@ def main():
     # and LDS leaves (README.md:647-650), 3 MSB pass + LSB passes inside its buckets
     how = int(last[1].hybrid) if (not sharded and hasattr(last[1], "hybrid")) else 0
     lsd_only = None
-    if not sharded and how != 0 and rank == 0:
+    if args.full and not sharded and how != 0 and rank == 0 and pool > 1:
         # the same workload with one pass per kept column (RSX_NO_HYBRID=1), a few steps, for comparison; not `value`
         os.environ["RSX_NO_HYBRID"] = "1"
         rsa.reload_env()
-        reps = min(K, 5)
+        reps = min(K, 5, pool - 1)
         for b in range(1 + reps):      # (the timed steps have sorted their batches in place: fresh ones)
             rsa.fill_splitmix(batches[b], seed=1001 + b, first_index=rank * n)
         step(0)
@@ -455,7 +512,9 @@ def main():
                 ("%d x 2^%d u32 keys sharded by MSD digit, RCCL all-to-all-v, local LSD (BASELINE.json configs[4])"
                  % (world, log2n)),
                 "keys_per_gpu": n, "total_keys": n * world, "generator": "splitmix64 seed 1+batch",
-                "parallelism": "msd%d" % world if sharded else "1 gpu", "output_sorted": ok, "output_checksums_match_input": True,
+                # (checked with --full only; None: not checked)
+                "parallelism": "msd%d" % world if sharded else "1 gpu", "output_sorted": ok,
+                "output_checksums_match_input": True if args.full else None,
                 "passes": {0: "one scatter pass per kept column, LSB first (radix_sort.hpp:82-90)",
                            1: "one MSB scatter pass, then the other kept columns per bucket in LDS (README.md:647-650)",
                            2: "two MSB scatter passes, then the other kept columns per bucket in LDS (README.md:647-650)",
@@ -509,7 +568,7 @@ def main():
             out["multi"] = {"phases_last_step_max_over_ranks_ms": phase_max, "safe_mode": bool(last[1].get("safe_mode")),
                             "safe_why": last[1].get("safe_why"), "overlap_stream": last[1].get("overlap_stream"),
                             "imbalance": last[1].get("imbalance")}
-        if world == 1 and not sharded and not args.no_cpu_baseline:
+        if args.full and world == 1 and not sharded and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
     if sharded:
         # the result line is the LAST thing the job prints: the other ranks go quiet, the process group is torn down

@@ -266,7 +266,7 @@ def test_bench_sharded_path_in_a_one_rank_group():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                          "--log2n", "22", "--force-exchange"], capture_output=True, text=True, timeout=600, env=_one_rank_env())
+                          "--log2n", "22", "--force-exchange", "--full"], capture_output=True, text=True, timeout=600, env=_one_rank_env())
     assert out.returncode == 0, out.stdout + out.stderr
     line = json.loads(out.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 1 and line["config"]["parallelism"] == "msd1" and line["config"]["output_sorted"] is True
@@ -427,7 +427,8 @@ def test_bench_launches_real_ranks():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "24"],
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--log2n", "24",
+                          "--full"],
                          capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-3000:]
     line = json.loads(out.stdout.strip().splitlines()[-1])

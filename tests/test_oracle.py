@@ -3,8 +3,9 @@
 Sources of truth, in order: the reference's own known-answer material
 (radix_tests.cpp literals, stdout tables of Listings 4-6, README.md:612-623),
 the committed golden table generated from the real headers
-(tests/golden/kat_table.json, tools/gen_golden.py), and -- where
-oracle/_ref/libref.so is present -- the real reference itself on randomized sweeps.
+(tests/golden/kat_table.json, tools/gen_golden.py), and the real reference on
+seeded randomized sweeps: its results recorded as hashes (tests/golden/ref_sweeps.json,
+tools/gen_golden.py) and, where oracle/_ref/libref.so is present, the reference itself.
 """
 import ctypes as C
 import json
@@ -19,7 +20,15 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 with open(os.path.join(GOLDEN, "kat_table.json")) as f:
     KAT = json.load(f)
 
-needs_ref = pytest.mark.skipif(ol.ref() is None, reason="oracle/_ref/libref.so not built (no /root/reference)")
+
+def ref_sweeps():
+    """tests/golden/ref_sweeps.json: the real reference's results on the seeded sweeps below"""
+    with open(os.path.join(GOLDEN, "ref_sweeps.json")) as f:
+        return json.load(f)
+
+
+def hx(a):
+    return "%016x" % ol.fnv1a64(a)
 
 
 def _id(row):
@@ -261,8 +270,11 @@ def test_oracle_hist_post_state_matches_golden(row):
     assert "%016x" % ol.fnv1a64(hist) == row["fnv_hist_u64"]
 
 
-@needs_ref
-def test_oracle_hist_post_state_vs_reference_sweep():
+# ---- seeded randomized sweeps against the real reference: its results are recorded in tests/golden/ref_sweeps.json
+# (tools/gen_golden.py, from these generators); where oracle/_ref/libref.so is built, the reference runs here as well
+
+def hist_sweep_cases():
+    """(dt, input, hvt_bytes) of the rs_sort_main-with-a-histogram sweep"""
     rng = np.random.default_rng(77)
     for trial in range(120):
         dt = int(rng.integers(0, 10))
@@ -272,16 +284,11 @@ def test_oracle_hist_post_state_vs_reference_sweep():
         a = ol.splitmix_fill(n, dt, int(rng.integers(1, 1 << 30)), mask)
         if trial % 5 == 4 and n:
             a = a[ol.stable_argsort_by_kdf(a, dt)]
-        hv = ol.hvt_bytes_for(n)
-        r1, r2 = ol.oracle_sort_main_hist(a, dt, hv), ol.ref_sort_main_hist(a, dt, hv)
-        assert r1[1] == r2[1] and np.array_equal(r1[0], r2[0]) and np.array_equal(r1[2], r2[2]), (dt, n, hex(mask))
+        yield dt, a, ol.hvt_bytes_for(n)
 
 
-# ---- randomized differential sweep against the real reference ------------------------------------
-
-@needs_ref
-@pytest.mark.parametrize("dt", range(10), ids=ol.DTYPE_NAMES)
-def test_oracle_vs_reference_sweep(dt):
+def sort_sweep_cases(dt):
+    """inputs of the radix_sort sweep of one dtype (each sorted in both orders)"""
     rng = np.random.default_rng(1234 + dt)
     full = (1 << (8 * ol.DTYPE_SIZE[dt])) - 1
     for trial in range(40):
@@ -296,27 +303,63 @@ def test_oracle_vs_reference_sweep(dt):
         a = ol.splitmix_fill(n, dt, int(rng.integers(1, 1 << 30)), mask)
         if trial % 7 == 6 and n:
             a = a[ol.stable_argsort_by_kdf(a, dt, trial & 1)]   # pre-sorted input -> early exit
+        yield a
+
+
+UNTOUCHED_MASKS = (0xFFFFFFFF, 0x00FFFFFF, 0xFF00, 0xFF)
+
+
+def sort_both_buffers(lib_sort, a):
+    """src and aux after one u32 sort of `a` (aux pre-filled with 0xA5) and the buffer returned"""
+    s, x = a.copy(), np.full_like(a, 0xA5)
+    return lib_sort(s, x), s, x
+
+
+def test_oracle_hist_post_state_vs_reference_sweep():
+    rows = ref_sweeps()["hist_sweep"]
+    cases = list(hist_sweep_cases())
+    assert len(cases) == len(rows) == 120
+    for (dt, a, hv), row in zip(cases, rows):
+        assert hx(a) == row["fnv_in"]
+        r1 = ol.oracle_sort_main_hist(a, dt, hv)
+        assert (hx(r1[0]), r1[1], hx(r1[2])) == (row["fnv_out"], row["result_in_aux"], row["fnv_hist_u64"]), (dt, a.size)
+        if ol.ref() is not None:
+            r2 = ol.ref_sort_main_hist(a, dt, hv)
+            assert r1[1] == r2[1] and np.array_equal(r1[0], r2[0]) and np.array_equal(r1[2], r2[2]), (dt, a.size)
+
+
+@pytest.mark.parametrize("dt", range(10), ids=ol.DTYPE_NAMES)
+def test_oracle_vs_reference_sweep(dt):
+    rows = ref_sweeps()["sort_sweep"][ol.DTYPE_NAMES[dt]]
+    cases = list(sort_sweep_cases(dt))
+    assert len(cases) == len(rows) == 40
+    for a, row in zip(cases, rows):
+        assert hx(a) == row["fnv_in"]
+        n = a.size
         for order in (ol.ASC, ol.DESC):
-            want, want_aux = ol.ref_sort(a, dt, order)
             got, got_aux, info = ol.oracle_sort(a, dt, order)
-            assert got_aux == want_aux
-            assert np.array_equal(got, want)
+            assert (hx(got), got_aux) == (row["fnv_out"][order], row["result_in_aux"][order]), (n, order)
+            if ol.ref() is not None:
+                want, want_aux = ol.ref_sort(a, dt, order)
+                assert got_aux == want_aux
+                assert np.array_equal(got, want)
             # the generic record path (rec_size == key size) is the same function
             src, aux = a.copy(), np.full_like(a, 0xA5)
             r = ol.oracle().rso_sort_records(ol.ptr(src), ol.ptr(aux), n, ol.DTYPE_SIZE[dt], 0, dt, order, None)
-            assert r == want_aux and np.array_equal(aux if r else src, want)
+            assert r == got_aux and np.array_equal(aux if r else src, got)
 
 
-@needs_ref
 def test_oracle_vs_reference_untouched_buffers():
     """The non-returned buffer holds the previous pass's data; both must match the reference byte for byte."""
-    for mask in (0xFFFFFFFF, 0x00FFFFFF, 0xFF00, 0xFF):
+    rows = ref_sweeps()["untouched"]
+    assert len(rows) == len(UNTOUCHED_MASKS)
+    for mask, row in zip(UNTOUCHED_MASKS, rows):
         a = ol.splitmix_fill(3000, ol.U32, 9, mask)
-        s1, a1 = a.copy(), np.full_like(a, 0xA5)
-        s2, a2 = a.copy(), np.full_like(a, 0xA5)
-        r1 = ol.ref().ref_sort(ol.ptr(s1), ol.ptr(a1), a.size, ol.U32, 0)
-        r2 = ol.oracle().rso_sort(ol.ptr(s2), ol.ptr(a2), a.size, ol.U32, 0, None)
-        assert r1 == r2 and np.array_equal(s1, s2) and np.array_equal(a1, a2)
+        r2, s2, a2 = sort_both_buffers(lambda s, x: ol.oracle().rso_sort(ol.ptr(s), ol.ptr(x), s.size, ol.U32, 0, None), a)
+        assert (r2, hx(s2), hx(a2)) == (row["result_in_aux"], row["fnv_src"], row["fnv_aux"]), hex(mask)
+        if ol.ref() is not None:
+            r1, s1, a1 = sort_both_buffers(lambda s, x: ol.ref().ref_sort(ol.ptr(s), ol.ptr(x), s.size, ol.U32, 0), a)
+            assert r1 == r2 and np.array_equal(s1, s2) and np.array_equal(a1, a2)
 
 
 @pytest.mark.parametrize("dt,order,mask,n", [(ol.F32, ol.ASC, 0xFFFFFFFF, 300001), (ol.F32, ol.DESC, 0xFFF000FF, 200000),

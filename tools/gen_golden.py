@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Generate tests/golden/* from the REAL reference (oracle/_ref/libref.so).
+"""Generate tests/golden/* from the REAL reference (oracle/_ref/libref.so):
+kat_table.json, test_int_input.bin and ref_sweeps.json (the seeded sweeps of tests/test_oracle.py).
 
 Run in the build container only (needs /root/reference to build oracle/_ref).
 What is committed is data: generator parameters, FNV-1a-64 hashes of inputs and
@@ -174,6 +175,33 @@ def main():
     with open(path, "w") as f:
         json.dump(out, f, indent=1)
     print("wrote", path, "rows:", len(out["scalar"]), len(out["scalar_extra"]), len(out["rank"]), len(out["hist_post"]))
+    write_ref_sweeps()
+
+
+def write_ref_sweeps():
+    """tests/golden/ref_sweeps.json: the real reference's results on tests/test_oracle.py's seeded sweeps (its case
+    generators), as FNV-1a-64 hashes of the inputs and outputs and which buffer was returned."""
+    import test_oracle as to
+    assert ol.ref() is not None, "oracle/_ref/libref.so is needed"
+    out = {"hist_sweep": [], "sort_sweep": {}, "untouched": []}
+    for dt, a, hv in to.hist_sweep_cases():
+        res, in_aux, hist = ol.ref_sort_main_hist(a, dt, hv)
+        out["hist_sweep"].append({"dtype": ol.DTYPE_NAMES[dt], "n": int(a.size), "hvt_bytes": hv, "fnv_in": hx(ol.fnv1a64(a)),
+                                  "fnv_out": hx(ol.fnv1a64(res)), "result_in_aux": in_aux, "fnv_hist_u64": hx(ol.fnv1a64(hist))})
+    for dt in range(10):
+        rows = out["sort_sweep"][ol.DTYPE_NAMES[dt]] = []
+        for a in to.sort_sweep_cases(dt):
+            res = [ol.ref_sort(a, dt, order) for order in (ol.ASC, ol.DESC)]
+            rows.append({"n": int(a.size), "fnv_in": hx(ol.fnv1a64(a)), "fnv_out": [hx(ol.fnv1a64(r)) for r, _ in res],
+                         "result_in_aux": [aux for _, aux in res]})
+    for mask in to.UNTOUCHED_MASKS:
+        a = ol.splitmix_fill(3000, ol.U32, 9, mask)
+        r, s, x = to.sort_both_buffers(lambda s, x: ol.ref().ref_sort(ol.ptr(s), ol.ptr(x), s.size, ol.U32, 0), a)
+        out["untouched"].append({"mask": hx(mask), "result_in_aux": r, "fnv_src": hx(ol.fnv1a64(s)), "fnv_aux": hx(ol.fnv1a64(x))})
+    path = os.path.join(ROOT, "tests", "golden", "ref_sweeps.json")
+    with open(path, "w") as f:
+        json.dump(out, f, indent=0)
+    print("wrote", path, "rows:", len(out["hist_sweep"]), sum(map(len, out["sort_sweep"].values())), len(out["untouched"]))
 
 
 if __name__ == "__main__":

@@ -8,7 +8,7 @@ cd "$(dirname "$0")/.."
 REPO=$PWD
 OUT=$REPO/gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py > $OUT/bench_line.json 2> $OUT/bench_err.txt
+python bench.py --full > $OUT/bench_line.json 2> $OUT/bench_err.txt
 python tools/bench_configs.py --out $OUT/bench_configs.json > $OUT/bench_configs.txt 2>&1
 python tools/size_sweep.py 2>&1 | grep -v amdgpu.ids > $OUT/size_sweep.txt
 (cd /tmp && $REPO/tools/radix_bench --device 0 --verify --min-time 0.2 2>&1 | grep -v amdgpu.ids > $OUT/radix_bench.txt)
