@@ -2100,8 +2100,10 @@ int blind_enqueue(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, int *enque
 	const bool rep4 = (c.hints & 1u) != 0 || (env().probe & 4u) != 0;
 	// 8-byte keys in which nothing below the level-1 digit varies above bit 32 (keys below 2^40: BASELINE.json's cfg 3 (ii), (iii)):
 	// the level-1 slots can hold low words -- all 256 of them then fit the caller's second buffer -- and the level-2 pass reads four
-	// bytes per key.  Both atom passes in both forms are enqueued; the sample decides (SegCtl::narrow == 2).
-	c.narrow1 = sizeof(KT) == 8 && atoms1 && atoms64 && lo != 0 && !rep4 && !env().no_narrow1 && (((uintptr_t)aux) & 63) == 0;
+	// bytes per key.  Both atom passes in both forms are enqueued; the sample decides (SegCtl::narrow == 2).  The 256 slots of cap1
+	// four-byte places must fit the caller's n keys (a larger cap1 -- RSX_CAP1_PAD_KIB -- would write past its end).
+	c.narrow1 = sizeof(KT) == 8 && atoms1 && atoms64 && lo != 0 && !rep4 && !env().no_narrow1 && (((uintptr_t)aux) & 63) == 0 &&
+	            (size_t)256 * cap1 * 4 <= n * sizeof(KT);
 	// the sample (workgroup 0: control block, plan) and the zeroing of both passes' status words, one launch
 	static_assert(sizeof(SegCtl) <= 256, "the control block is not part of what is zeroed");
 	RSX_TRY(blind_forget_device_backoff(c));
