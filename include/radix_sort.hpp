@@ -273,6 +273,26 @@ T *radix_sort_multi(T *RESTRICT src, T *RESTRICT aux, size_t n, const int *devic
 	return static_cast<T *>(result);
 }
 
+// Not in the reference's header (its README's "Uniquely sorting with bitmaps", bitmap_sort_16.c): the DISTINCT elements in
+// order of kf(element) -- distinct bit patterns: -0.0f and +0.0f are two -- in the returned buffer (src or aux; src is
+// consumed), their number in *n_unique (rsx_sort_unique).  Scalar T with basic_kdfs::kdf or rsx_kdf::descending<T>.
+template <typename T, typename KeyFunc = decltype(basic_kdfs::kdf<T>)>
+T *radix_sort_unique(T *RESTRICT src, T *RESTRICT aux, size_t n, size_t *n_unique, KeyFunc &&kf = basic_kdfs::kdf<T>)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, KeyFunc> || rsx_detail::is_descending_kdf_v<T, KeyFunc>,
+	              "radix_sort_unique takes scalar keys with basic_kdfs::kdf or rsx_kdf::descending");
+	if constexpr (rsx_detail::may_be_default_kdf_v<T, KeyFunc>)
+		if (!rsx_detail::kdf_kind<T, KeyFunc>::is_default(kf))
+			throw std::invalid_argument("radix_sort_unique: a function other than basic_kdfs::kdf<T> was passed as KeyFunc");
+	void *result = nullptr;
+	const int rc = rsx_sort_unique(src, aux, n, rsx_detail::dtype_of<T>(),
+	                               rsx_detail::is_descending_kdf_v<T, KeyFunc> ? RSX_DESCENDING : RSX_ASCENDING, nullptr, 0, &result,
+	                               n_unique, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_unique", rc);
+	return static_cast<T *>(result);
+}
+
 // The reference lets the caller supply the histogram storage (any container with value_type and
 // operator[], pre-zeroed, 256 * sizeof(KeyType) entries: radix_sort.hpp:28-33).  The device keeps its own counters;
 // the counts of its histogram pass are brought back (rsx_capture_histogram) and `histogram` is left in the state the

@@ -50,6 +50,11 @@
  *   If an allocation fails the sort takes the histogram-first
  *   route and the (device, stream) context does not ask again until rsx_reload_env() or rsx_release_stream();
  *   RSX_NO_BLIND=1 never asks.
+ *   rsx_sort_unique*: the bitmap is at most 2^RSX_UNIQUE_MAX_BITS / 8 bytes (2 MiB by default, 128 MiB at the compiled
+ *   maximum of 30 bits), plus 16 bytes per 4 KiB of it and per tile of 8192 4-byte keys of a compaction.  It lives in the
+ *   (device, stream) context like every other buffer here and is freed by rsx_release / rsx_release_stream.  It is never
+ *   allocated inside a stream capture (the call refuses a capturing stream: it waits for the number of distinct keys).  If
+ *   its allocation fails the call takes the sort route.
  *
  * Environment switches (read ONCE, at the library's first call; rsx_reload_env() reads them again)
  *   RSX_VERIFY=1            after every scatter pass one tile is re-ranked without LDS
@@ -103,6 +108,9 @@
  *   RSX_NO_SMALL_SORT, RSX_NO_HOST_SMALL, RSX_NO_FILL_RUNS, RSX_NO_SMALL_TILES, RSX_NO_SPECULATION,
  *   RSX_NO_NARROW_KEYS
  *                           switch single optimisations off (tests).
+ *   RSX_UNIQUE_MAX_BITS=k   rsx_sort_unique*: the widest bitmap is 2^k bits (default 24, at most 30); 0: never a bitmap or a
+ *                           count table -- everything but all-equal keys goes through the sort and one compaction (tests
+ *                           force that route with it, tools/unique_probe.py sweeps the cut-off);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
  */
 #ifndef RSX_H
@@ -295,6 +303,46 @@ int rsx_capture_histogram(uint64_t *hist, size_t entries);
  * waited for: the result is valid for work ordered after them on `stream`. */
 int rsx_sort_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, rsx_order order,
                     void *stream, void **result, rsx_info *info);
+
+/* ---- sorted distinct keys ("Uniquely sorting with bitmaps", README.md, bitmap_sort_16.c) ------------------ */
+
+/* The distinct keys of the input in order of kdf(key), and optionally how many of each.
+ *   - Result: *result is d_src or d_aux; its first *n_unique elements are the distinct BIT PATTERNS of the input,
+ *     ascending by kdf(key) (RSX_DESCENDING: by the complemented KDF).  The KDF is a bijection on bit patterns, so
+ *     "distinct" is by bit pattern -- the "bit-exact copies" rule above: -0.0 and +0.0 are two keys, NaNs with different
+ *     payloads are different keys.
+ *   - Buffers: d_src is consumed, as by rsx_sort_device; everything past *n_unique in both buffers is unspecified.
+ *   - n < 2 returns d_src with *n_unique = n and leaves d_aux untouched; no device is needed for that, except to write
+ *     the one count of n == 1 into device memory (rsx_sort_unique writes it into host memory itself).
+ *   - Counts: d_counts may be NULL; otherwise it has room for n entries of count_bytes = 4 or 8 (with 4, n must fit, or
+ *     the call fails with RSX_EINVAL "does not fit", as for idx_bytes), and counts[j] = the number of input elements
+ *     equal to result[j].
+ *   - Blocking: the call returns once *n_unique is on the host; the arrays are valid for work ordered after it on `stream`.
+ *   - Errors: no GPU: RSX_ENODEVICE; bad dtype, order or count_bytes: RSX_EINVAL.  A failed allocation of the bitmap is
+ *     not an error: the call takes the sort route.
+ * The route is chosen from what the call can observe of the keys (rsx_unique_info.route): where few bits of
+ * the derived keys vary, one bit per possible value replaces the sort; where one byte column varies (all 1-byte keys), or
+ * counts of 2-byte keys are wanted, the answer is read off a count table; everything else is rsx_sort_device -- any of its
+ * routes, every early exit -- and one compaction of the sorted buffer into the other one. */
+enum { RSX_UNIQUE_TRIVIAL = 0,        /* n < 2, or every key equal                                   */
+       RSX_UNIQUE_BITMAP_LDS = 1,     /* per-workgroup bitmaps in LDS, merged into one in HBM        */
+       RSX_UNIQUE_BITMAP_GLOBAL = 2,  /* one bitmap in device memory                                 */
+       RSX_UNIQUE_TABLE = 3,          /* answer read off a count table that already exists           */
+       RSX_UNIQUE_SORT = 4 };         /* the ordinary sort (any route), then one compaction          */
+typedef struct rsx_unique_info {
+	rsx_info sort;          /* front half: key_bytes, kept columns, early_exit; hybrid as the sort reports it on RSX_UNIQUE_SORT */
+	uint32_t route;         /* RSX_UNIQUE_*                                                          */
+	uint32_t varying_bits;  /* popcount of the KDF bits that differ among the keys; 0 = not computed */
+	uint64_t table_bytes;   /* bitmap / count table used, 0 otherwise                                */
+} rsx_unique_info;
+
+int rsx_sort_unique_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, rsx_order order,
+                           void *d_counts, size_t count_bytes, void *stream,
+                           void **result, size_t *n_unique, rsx_unique_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind); the distinct keys of host buffers come back into src or aux */
+int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order,
+                    void *counts, size_t count_bytes,
+                    void **result, size_t *n_unique, rsx_unique_info *info);
 
 /* ---- key + payload (struct-of-arrays) ------------------------------------- */
 

@@ -48,9 +48,19 @@ class Info(C.Structure):
         return [int(self.cols[i]) for i in range(self.ncols)]
 
 
+# rsx_unique_info.route
+UNIQUE_TRIVIAL, UNIQUE_BITMAP_LDS, UNIQUE_BITMAP_GLOBAL, UNIQUE_TABLE, UNIQUE_SORT = range(5)
+
+
+class UniqueInfo(C.Structure):
+    """rsx_unique_info: the route rsx_sort_unique* took and what the front half of the sort decided."""
+    _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
+
+
 # every symbol include/rsx.h declares: (name, restype, argtypes)
 _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
+_PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -70,6 +80,8 @@ ABI = [
     ("rsx_sort_pairs_inplace_async", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP]),
     ("rsx_capture_histogram", _I, [_VP, _SZ]),
     ("rsx_sort_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _PVP, _PINFO]),
+    ("rsx_sort_unique_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _VP, _PVP, _PSZ, _PUINFO]),
+    ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
     ("rsx_sort_rank", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _PVP, _PINFO]),
     ("rsx_sort_rank_device", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _VP, _PVP, _PINFO]),
@@ -228,6 +240,31 @@ def radix_sort(src, aux, dtype=None, order=ASCENDING, stream=None):
     check(lib().rsx_sort_device(src.data_ptr(), aux.data_ptr(), src.numel(), code, order, _stream_ptr(stream),
                                 C.byref(res), C.byref(info)))
     return (aux if info.result_in_aux else src), info
+
+
+def radix_sort_unique(src, aux, dtype=None, order=ASCENDING, counts=None, stream=None):
+    """rsx_sort_unique_device: the distinct keys of ``src`` in order of kdf(key) (distinct BIT PATTERNS: -0.0 and +0.0 are two).
+
+    Returns (result[:n_unique], counts[:n_unique] or None, info): ``result`` is ``src`` or ``aux``; ``counts`` is an int32 /
+    int64 (or uint32 / uint64) device tensor with room for n entries that receives how often each distinct key occurs.
+    ``src`` is consumed; the call returns once n_unique is known."""
+    _check_dev(src, aux)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    _same_shape(src, aux, "aux")
+    cptr, cbytes = None, 0
+    if counts is not None:
+        _check_dev(counts)
+        cbytes = counts.element_size()
+        if counts.numel() < src.numel():
+            raise RsxError("counts must have room for n entries")
+        cptr = counts.data_ptr()
+    res, nu, info = C.c_void_p(), C.c_size_t(0), UniqueInfo()
+    check(lib().rsx_sort_unique_device(src.data_ptr(), aux.data_ptr(), src.numel(), code, order, cptr, cbytes, _stream_ptr(stream),
+                                       C.byref(res), C.byref(nu), C.byref(info)))
+    out = aux if (src.numel() and res.value == aux.data_ptr() and res.value != src.data_ptr()) else src
+    return out[:nu.value], (None if counts is None else counts[:nu.value]), info
 
 
 HINT_EVEN_TOP_DIGITS = 1
@@ -408,6 +445,17 @@ def radix_sort_host(src, aux, dtype, order=ASCENDING):
     res, info = C.c_void_p(), Info()
     check(lib().rsx_sort(src.ctypes.data, aux.ctypes.data, src.size, dtype, order, C.byref(res), C.byref(info)))
     return (aux if info.result_in_aux else src), info
+
+
+def radix_sort_unique_host(src, aux, dtype, order=ASCENDING, counts=None):
+    """rsx_sort_unique on host numpy buffers; returns (result[:n_unique], counts[:n_unique] or None, info).  ``counts``: a
+    numpy array of 4- or 8-byte integers with room for n entries."""
+    res, nu, info = C.c_void_p(), C.c_size_t(0), UniqueInfo()
+    cptr, cbytes = (None, 0) if counts is None else (counts.ctypes.data, counts.itemsize)
+    check(lib().rsx_sort_unique(src.ctypes.data, aux.ctypes.data, src.size, dtype, order, cptr, cbytes, C.byref(res), C.byref(nu),
+                                C.byref(info)))
+    out = aux if (src.size and res.value == aux.ctypes.data and res.value != src.ctypes.data) else src
+    return out[:nu.value], (None if counts is None else counts[:nu.value]), info
 
 
 def radix_sort_multi_host(src, aux, dtype, order=ASCENDING, devices=None):
