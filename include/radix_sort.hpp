@@ -293,6 +293,21 @@ T *radix_sort_unique(T *RESTRICT src, T *RESTRICT aux, size_t n, size_t *n_uniqu
 	return static_cast<T *>(result);
 }
 
+// Not in the reference's header (its README's "Hybrids" note): the first k elements of the stable sorted order of src, which
+// is not written, into out (room for k), and their positions in src into idx if given (room for k; equal keys in ascending
+// index order, as radix_sort_rank orders them).  Returns k.  Scalar T with basic_kdfs::kdf; RSX_DESCENDING for the
+// complemented order (rsx_sort_topk).
+template <typename T, typename IdxType = uint32_t>
+size_t radix_sort_topk(const T *src, size_t n, size_t k, T *out, IdxType *idx = nullptr, rsx_order order = RSX_ASCENDING)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_topk takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_topk: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_topk(src, n, k, rsx_detail::dtype_of<T>(), order, out, idx, sizeof(IdxType), nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_topk", rc);
+	return k;
+}
+
 // The reference lets the caller supply the histogram storage (any container with value_type and
 // operator[], pre-zeroed, 256 * sizeof(KeyType) entries: radix_sort.hpp:28-33).  The device keeps its own counters;
 // the counts of its histogram pass are brought back (rsx_capture_histogram) and `histogram` is left in the state the

@@ -55,6 +55,11 @@
  *   (device, stream) context like every other buffer here and is freed by rsx_release / rsx_release_stream.  It is never
  *   allocated inside a stream capture (the call refuses a capturing stream: it waits for the number of distinct keys).  If
  *   its allocation fails the call takes the sort route.
+ *   rsx_sort_topk*: the select route keeps, in the (device, stream) context, a candidate buffer of n / 8 + 1024 (key, index)
+ *   pairs, 4 x k keys and indices (the k pairs and the second buffers of their sort) and about 2 MiB of counts per
+ *   workgroup; the sort route keeps what rsx_sort_rank keeps (2 n indices and the rank sort's workspace).  All of it is
+ *   freed by rsx_release / rsx_release_stream and never allocated inside a stream capture (the call refuses a capturing
+ *   stream).  If an allocation of the select route fails the call takes the sort route.
  *
  * Environment switches (read ONCE, at the library's first call; rsx_reload_env() reads them again)
  *   RSX_VERIFY=1            after every scatter pass one tile is re-ranked without LDS
@@ -111,6 +116,8 @@
  *   RSX_UNIQUE_MAX_BITS=k   rsx_sort_unique*: the widest bitmap is 2^k bits (default 24, at most 30); 0: never a bitmap or a
  *                           count table -- everything but all-equal keys goes through the sort and one compaction (tests
  *                           force that route with it, tools/unique_probe.py sweeps the cut-off);
+ *   RSX_TOPK_FORCE=1        rsx_sort_topk*: the select route whenever n >= 2 and 0 < k <= n; =2: always the sort route
+ *                           (tests run both and compare; tools/topk_probe.py times both);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
  */
 #ifndef RSX_H
@@ -343,6 +350,46 @@ int rsx_sort_unique_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, 
 int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order,
                     void *counts, size_t count_bytes,
                     void **result, size_t *n_unique, rsx_unique_info *info);
+
+/* ---- the first k of the sorted order ("Hybrids", README.md:647-650: one MSB pass, then only the sub-result that matters) -- */
+
+/* The first k entries of the stable sorted order, without sorting the rest.
+ *   - Result: out_idx[j], j < k, is the j-th entry of what rsx_sort_rank returns for the same keys, dtype and order: a
+ *     stable argsort, so equal keys come in ascending index order -- also among the keys equal to the k-th one, of which
+ *     the lowest indices are kept.  out_keys[j] is the bit-exact image of src[out_idx[j]] (NaN payloads, -0.0).
+ *     RSX_DESCENDING orders by the complemented KDF; ties still come in ascending index order.
+ *   - Buffers: d_src is never written.  Each output has room for exactly k elements and nothing past element k - 1 is
+ *     touched.  Either output may be NULL, not both.  idx_bytes is 4 or 8; with 4, n must fit, or the call fails with
+ *     RSX_EINVAL "does not fit".
+ *   - Errors: k > n: RSX_EINVAL "k exceeds n"; bad dtype, order, idx_bytes, both outputs NULL: RSX_EINVAL; k == 0: RSX_OK,
+ *     nothing written, no device needed; k > 0 without a GPU: RSX_ENODEVICE, nothing written; a capturing stream:
+ *     RSX_EINVAL (the call waits for what the selection found).
+ *   - Blocking: as rsx_sort_device -- the call may synchronise `stream`; the outputs are valid for work ordered after it
+ *     on `stream`; *info is complete on return.
+ * RSX_TOPK_SELECT: a histogram of the keys' most significant byte tells which bucket holds rank k; one more
+ * pass over the input moves that bucket into a candidate buffer, the remaining bytes are found there, and the k surviving
+ * (key, index) pairs go through the ordinary stable key + payload sort.  A bucket too large for the candidate buffer is
+ * narrowed by further histograms over the input instead: input_reads <= key_bytes + 1 always, 2 for keys that spread over
+ * their top byte.  RSX_TOPK_SORT is rsx_sort_rank_device on a workspace copy, the first k ranks kept (small n, large k). */
+enum { RSX_TOPK_TRIVIAL = 0,   /* k == 0, or n < 2                                              */
+       RSX_TOPK_SELECT  = 1,   /* MSD radix select, then a sort of k candidates                 */
+       RSX_TOPK_SORT    = 2 }; /* the ordinary stable rank sort, first k kept                   */
+typedef struct rsx_topk_info {
+	uint32_t route;        /* RSX_TOPK_*                                                         */
+	uint32_t key_bytes;
+	uint32_t input_reads;  /* SELECT: kernels that read all n keys of d_src; otherwise 0         */
+	uint32_t digit_passes; /* SELECT: histogram passes made, over the input or the candidates    */
+	uint64_t n_less;       /* elements with kdf(key) <  kdf(k-th key)  (always < k)              */
+	uint64_t n_equal;      /* elements with kdf(key) == kdf(k-th key)  (n_less + n_equal >= k)   */
+	uint64_t kth_key;      /* bit pattern of the k-th element, zero-extended                     */
+} rsx_topk_info;
+
+int rsx_sort_topk_device(const void *d_src, size_t n, size_t k, rsx_dtype dtype, rsx_order order,
+                         void *d_out_keys, void *d_out_idx, size_t idx_bytes,
+                         void *stream, rsx_topk_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind) */
+int rsx_sort_topk(const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_order order,
+                  void *out_keys, void *out_idx, size_t idx_bytes, rsx_topk_info *info);
 
 /* ---- key + payload (struct-of-arrays) ------------------------------------- */
 

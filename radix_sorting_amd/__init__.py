@@ -57,10 +57,21 @@ class UniqueInfo(C.Structure):
     _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
 
 
+# rsx_topk_info.route
+TOPK_TRIVIAL, TOPK_SELECT, TOPK_SORT = range(3)
+
+
+class TopkInfo(C.Structure):
+    """rsx_topk_info: the route rsx_sort_topk* took and what it found about the k-th key."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("input_reads", C.c_uint32), ("digit_passes", C.c_uint32),
+                ("n_less", C.c_uint64), ("n_equal", C.c_uint64), ("kth_key", C.c_uint64)]
+
+
 # every symbol include/rsx.h declares: (name, restype, argtypes)
 _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
 _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
+_PTINFO = C.POINTER(TopkInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -82,6 +93,8 @@ ABI = [
     ("rsx_sort_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _PVP, _PINFO]),
     ("rsx_sort_unique_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _VP, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
+    ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
+    ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
     ("rsx_sort_rank", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _PVP, _PINFO]),
     ("rsx_sort_rank_device", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _VP, _PVP, _PINFO]),
@@ -265,6 +278,35 @@ def radix_sort_unique(src, aux, dtype=None, order=ASCENDING, counts=None, stream
                                        C.byref(res), C.byref(nu), C.byref(info)))
     out = aux if (src.numel() and res.value == aux.data_ptr() and res.value != src.data_ptr()) else src
     return out[:nu.value], (None if counts is None else counts[:nu.value]), info
+
+
+def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
+    """rsx_sort_topk_device: the first ``k`` entries of the stable sorted order of ``src``, which is not written.
+
+    Returns (keys, idx or None, info): ``keys[j]`` is the bit-exact image of ``src[idx[j]]`` and ``idx`` the first k entries
+    of radix_sort_rank's result (equal keys in ascending index order).  Outputs of k elements are allocated when none are
+    given: ``keys`` of src's dtype, ``idx`` int32 when n < 2^31, otherwise int64 (``want_idx=False``: no indices)."""
+    import torch
+    _check_dev(src)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    n, k = src.numel(), int(k)
+    if keys_out is None:
+        keys_out = torch.empty(k, dtype=src.dtype, device=src.device)
+    if idx_out is None and want_idx:
+        idx_out = torch.empty(k, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=src.device)
+    for t, what, size in ((keys_out, "keys_out", src.element_size()), (idx_out, "idx_out", None)):
+        if t is None:
+            continue
+        _check_dev(t)
+        if t.numel() < k or (size is not None and t.element_size() != size):
+            raise RsxError("%s must have room for k elements of the right size" % what)
+    info = TopkInfo()
+    check(lib().rsx_sort_topk_device(src.data_ptr(), n, k, code, order, keys_out.data_ptr(),
+                                     None if idx_out is None else idx_out.data_ptr(),
+                                     4 if idx_out is None else idx_out.element_size(), _stream_ptr(stream), C.byref(info)))
+    return keys_out[:k], (None if idx_out is None else idx_out[:k]), info
 
 
 HINT_EVEN_TOP_DIGITS = 1
@@ -456,6 +498,21 @@ def radix_sort_unique_host(src, aux, dtype, order=ASCENDING, counts=None):
                                 C.byref(info)))
     out = aux if (src.size and res.value == aux.ctypes.data and res.value != src.ctypes.data) else src
     return out[:nu.value], (None if counts is None else counts[:nu.value]), info
+
+
+def radix_sort_topk_host(src, k, dtype, order=ASCENDING, want_idx=True, idx_dtype=None):
+    """rsx_sort_topk on a host numpy buffer; returns (keys, idx or None, info) as radix_sort_topk does (``idx_dtype``: a
+    4- or 8-byte numpy integer type; default uint32 when n < 2^32, otherwise uint64)."""
+    import numpy as np
+    k = int(k)
+    keys = np.empty(k, dtype=src.dtype)
+    idx = None
+    if want_idx:
+        idx = np.empty(k, dtype=idx_dtype if idx_dtype is not None else (np.uint32 if src.size < 2 ** 32 else np.uint64))
+    info = TopkInfo()
+    check(lib().rsx_sort_topk(src.ctypes.data, src.size, k, dtype, order, keys.ctypes.data, None if idx is None else idx.ctypes.data,
+                              4 if idx is None else idx.itemsize, C.byref(info)))
+    return keys, idx, info
 
 
 def radix_sort_multi_host(src, aux, dtype, order=ASCENDING, devices=None):
