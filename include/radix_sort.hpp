@@ -308,6 +308,33 @@ size_t radix_sort_topk(const T *src, size_t n, size_t k, T *out, IdxType *idx = 
 	return k;
 }
 
+// Not in the reference's header (its text's stability argument one level up): the stable argsort of n rows by several key
+// columns, none of which is written, into idx_out (room for n).  c0 is the MOST significant column, as in ORDER BY c0, c1, ...
+// (np.lexsort takes its keys in the reverse order); rows equal in every column come in ascending index order.  Scalar column
+// types with basic_kdfs::kdf, ascending; for per-column orders (or types only known at run time) pass an array of rsx_lex_col
+// (rsx_sort_lex).  Returns idx_out.
+template <typename IdxType>
+IdxType *radix_sort_lex(IdxType *idx_out, size_t n, const rsx_lex_col *cols, size_t ncols)
+{
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_lex: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_lex(cols, ncols, n, idx_out, sizeof(IdxType), nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_lex", rc);
+	return idx_out;
+}
+
+template <typename IdxType, typename T0, typename... Ts>
+IdxType *radix_sort_lex(IdxType *idx_out, size_t n, const T0 *c0, const Ts *...cs)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T0, decltype(basic_kdfs::kdf<T0>)> &&
+	              (rsx_detail::may_be_default_kdf_v<Ts, decltype(basic_kdfs::kdf<Ts>)> && ...),
+	              "radix_sort_lex takes columns of the scalar keys basic_kdfs::kdf accepts");
+	static_assert(1 + sizeof...(Ts) <= RSX_LEX_MAX_COLS, "radix_sort_lex: at most RSX_LEX_MAX_COLS columns");
+	const rsx_lex_col cols[] = {{c0, (uint32_t)rsx_detail::dtype_of<T0>(), (uint32_t)RSX_ASCENDING},
+	                            {cs, (uint32_t)rsx_detail::dtype_of<Ts>(), (uint32_t)RSX_ASCENDING}...};
+	return radix_sort_lex<IdxType>(idx_out, n, cols, 1 + sizeof...(Ts));
+}
+
 // The reference lets the caller supply the histogram storage (any container with value_type and
 // operator[], pre-zeroed, 256 * sizeof(KeyType) entries: radix_sort.hpp:28-33).  The device keeps its own counters;
 // the counts of its histogram pass are brought back (rsx_capture_histogram) and `histogram` is left in the state the

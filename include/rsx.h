@@ -60,6 +60,11 @@
  *   workgroup; the sort route keeps what rsx_sort_rank keeps (2 n indices and the rank sort's workspace).  All of it is
  *   freed by rsx_release / rsx_release_stream and never allocated inside a stream capture (the call refuses a capturing
  *   stream).  If an allocation of the select route fails the call takes the sort route.
+ *   rsx_sort_lex*: in the (device, stream) context, apart from what its inner rank and key + payload sorts keep: 3 n indices
+ *   of idx_bytes (the permutation and the second buffers of its sorts) and, unless the call is one lone column, 2 n keys of
+ *   the widest packed type (2, 4 or 8 bytes); rsx_sort_lex on host buffers also the staged columns and n indices.  Freed by
+ *   rsx_release / rsx_release_stream, never allocated inside a stream capture (the call refuses a capturing stream); a
+ *   failed allocation fails the call with RSX_ENOMEM.
  *
  * Environment switches (read ONCE, at the library's first call; rsx_reload_env() reads them again)
  *   RSX_VERIFY=1            after every scatter pass one tile is re-ranked without LDS
@@ -118,6 +123,8 @@
  *                           force that route with it, tools/unique_probe.py sweeps the cut-off);
  *   RSX_TOPK_FORCE=1        rsx_sort_topk*: the select route whenever n >= 2 and 0 < k <= n; =2: always the sort route
  *                           (tests run both and compare; tools/topk_probe.py times both);
+ *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
+ *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
  */
 #ifndef RSX_H
@@ -390,6 +397,55 @@ int rsx_sort_topk_device(const void *d_src, size_t n, size_t k, rsx_dtype dtype,
 /* host or device pointers, as rsx_sort (all of the same kind) */
 int rsx_sort_topk(const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_order order,
                   void *out_keys, void *out_idx, size_t idx_bytes, rsx_topk_info *info);
+
+/* ---- ordering by several key columns (the stability argument one level up: README.md, "this is only possible because
+ *      the sort is stable") ------------------------------------------------------------------------------------------ */
+
+/* The stable argsort of n rows by the tuple (kdf_0(col_0[i]), kdf_1(col_1[i]), ...).
+ *   - Result: out_idx[0 .. n-1] lists the rows in order of that tuple.  Column 0 is the MOST significant one, as in SQL's
+ *     ORDER BY col_0, col_1, ... -- the REVERSE of np.lexsort's argument order, whose last key is the primary one.  Each
+ *     column has its own dtype and its own order; RSX_DESCENDING complements that column's KDF.  Rows whose derived keys are
+ *     equal in every column come in ascending index order.  With ncols == 1 the result is element for element what
+ *     rsx_sort_rank_device returns for that column.
+ *   - Buffers: no column is ever written.  out_idx has room for exactly n entries of idx_bytes (4 or 8) and nothing past
+ *     entry n - 1 is touched; the ping-pong buffers are the library's (see "Scratch memory"), not the caller's.  With
+ *     idx_bytes == 4, n must fit, or the call fails with RSX_EINVAL "does not fit".  The `cols` array itself is host memory
+ *     in both forms.  The same column pointer may appear more than once.  A column needs only its element's alignment.
+ *   - Errors: ncols == 0 or ncols > RSX_LEX_MAX_COLS, a NULL column, a bad dtype or order, a bad idx_bytes: RSX_EINVAL.
+ *     n == 0: RSX_OK, no device needed.  n == 1 writes out_idx[0] = 0 (rsx_sort_lex on host pointers needs no device for
+ *     it, rsx_sort_lex_device only for that store).  Otherwise, without a GPU: RSX_ENODEVICE, nothing written.  A capturing
+ *     stream: RSX_EINVAL (the call waits between its sorts).  A failed allocation of the library's buffers: RSX_ENOMEM --
+ *     there is no cheaper route to fall back to.
+ *   - Blocking: as rsx_sort_device -- the call may synchronise `stream`; the output is valid for work ordered after it on
+ *     `stream`; *info is complete on return.
+ * How: neighbouring columns are GROUPED -- walking from the last column towards column 0, a column joins
+ * the current group while the group's bytes plus its own are at most the packing limit P (RSX_LEX_PACK_BYTES, default 4);
+ * a column wider than P is a group of its own.  One kernel (rsx_lex.hpp) derives and packs a group's keys into one unsigned
+ * key per row, the group's first column in the highest bits; group[0] -- the LEAST significant columns -- is rank-sorted
+ * (a lone column directly in the caller's memory, with its own dtype and order), every later group's keys are gathered
+ * through the permutation found so far and sorted stably with that permutation as their payload. */
+enum { RSX_LEX_MAX_COLS = 16 };
+typedef struct rsx_lex_col { const void *data; uint32_t dtype; uint32_t order; } rsx_lex_col;   /* rsx_dtype, rsx_order */
+
+typedef struct rsx_lex_group {
+	uint32_t first_col, ncols;   /* the columns first_col .. first_col + ncols - 1 of the call                  */
+	uint32_t key_bytes;          /* sum of their widths, 1 .. 8                                                */
+	uint32_t sorted_as;          /* rsx_dtype handed to the inner sort (the column's own for a lone column of group 0) */
+	uint32_t kept_cols, hybrid;  /* rsx_info.ncols / .hybrid of that sort                                      */
+	uint32_t in_order;           /* 1: that sort took its pre-sorted exit (the permutation did not change)     */
+	uint32_t pad;
+} rsx_lex_group;
+typedef struct rsx_lex_info {
+	uint32_t ncols, ngroups;     /* ngroups = sorts made; 0 when n < 2                                          */
+	uint32_t pack_bytes;         /* the packing limit in force (above)                                         */
+	uint32_t early_exit;         /* 0; 1: n < 2; 2: every group was in order, the result is 0 .. n-1           */
+	rsx_lex_group group[RSX_LEX_MAX_COLS];   /* group[0] is sorted FIRST = the least significant columns       */
+} rsx_lex_info;
+
+int rsx_sort_lex_device(const rsx_lex_col *cols, size_t ncols, size_t n, void *d_out_idx, size_t idx_bytes,
+                        void *stream, rsx_lex_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind); host columns are staged, each distinct one once */
+int rsx_sort_lex(const rsx_lex_col *cols, size_t ncols, size_t n, void *out_idx, size_t idx_bytes, rsx_lex_info *info);
 
 /* ---- key + payload (struct-of-arrays) ------------------------------------- */
 

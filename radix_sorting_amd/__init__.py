@@ -67,11 +67,35 @@ class TopkInfo(C.Structure):
                 ("n_less", C.c_uint64), ("n_equal", C.c_uint64), ("kth_key", C.c_uint64)]
 
 
+LEX_MAX_COLS = 16
+
+
+class LexCol(C.Structure):
+    """rsx_lex_col: one key column of rsx_sort_lex* (column 0 is the most significant one)."""
+    _fields_ = [("data", C.c_void_p), ("dtype", C.c_uint32), ("order", C.c_uint32)]
+
+
+class LexGroup(C.Structure):
+    """rsx_lex_group: the columns that were packed into one key and what the inner sort of that key reported."""
+    _fields_ = [("first_col", C.c_uint32), ("ncols", C.c_uint32), ("key_bytes", C.c_uint32), ("sorted_as", C.c_uint32),
+                ("kept_cols", C.c_uint32), ("hybrid", C.c_uint32), ("in_order", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class LexInfo(C.Structure):
+    """rsx_lex_info: how rsx_sort_lex* grouped the columns; group[0] was sorted first (the least significant columns)."""
+    _fields_ = [("ncols", C.c_uint32), ("ngroups", C.c_uint32), ("pack_bytes", C.c_uint32), ("early_exit", C.c_uint32),
+                ("group", LexGroup * LEX_MAX_COLS)]
+
+    def groups(self):
+        return [(int(g.first_col), int(g.ncols), int(g.key_bytes), int(g.sorted_as)) for g in self.group[:self.ngroups]]
+
+
 # every symbol include/rsx.h declares: (name, restype, argtypes)
 _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
 _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 _PTINFO = C.POINTER(TopkInfo)
+_PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -95,6 +119,8 @@ ABI = [
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
     ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
+    ("rsx_sort_lex_device", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _VP, _PLINFO]),
+    ("rsx_sort_lex", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _PLINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
     ("rsx_sort_rank", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _PVP, _PINFO]),
     ("rsx_sort_rank_device", _I, [_VP, _VP, _SZ, _I, _SZ, _I, _VP, _PVP, _PINFO]),
@@ -309,6 +335,49 @@ def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=
     return keys_out[:k], (None if idx_out is None else idx_out[:k]), info
 
 
+def _lex_cols(ptrs, codes, orders):
+    n = len(ptrs)
+    if orders is None:
+        orders = [ASCENDING] * n
+    if len(codes) != n or len(orders) != n:
+        raise RsxError("orders / dtypes must have one entry per column")
+    arr = (LexCol * max(n, 1))()
+    for i in range(n):
+        arr[i].data, arr[i].dtype, arr[i].order = ptrs[i], codes[i], orders[i]
+    return arr
+
+
+def radix_sort_lex(cols, orders=None, dtypes=None, idx_out=None, stream=None):
+    """rsx_sort_lex_device: the stable argsort of the rows of ``cols`` (device tensors of one length, none of them written).
+
+    ``cols[0]`` is the MOST significant column, as in ORDER BY -- the reverse of ``np.lexsort``'s argument order.  ``orders``
+    and ``dtypes`` give one rsx_order / rsx_dtype code per column (default: ascending, the tensor's own type).  Returns
+    (idx, info): ``idx`` is int32 when n < 2^31, otherwise int64, unless ``idx_out`` (n 4- or 8-byte entries) is given."""
+    import torch
+    cols = list(cols)
+    if cols:
+        _check_dev(*cols)
+    n = cols[0].numel() if cols else 0
+    codes = [_torch_dtype_code(t) for t in cols] if dtypes is None else list(dtypes)
+    if len(codes) != len(cols):
+        raise RsxError("orders / dtypes must have one entry per column")
+    for t, code in zip(cols, codes):
+        if t.numel() != n:
+            raise RsxError("every column must have the same number of elements")
+        if 0 <= code < len(DTYPE_SIZE) and t.element_size() != DTYPE_SIZE[code]:
+            raise RsxError("a column does not match its key type")
+    if idx_out is None:
+        dev = cols[0].device if cols else "cuda"
+        idx_out = torch.empty(n, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=dev)
+    _check_dev(idx_out)
+    if idx_out.numel() < n:
+        raise RsxError("idx_out must have room for n entries")
+    arr = _lex_cols([t.data_ptr() for t in cols], codes, orders)
+    info = LexInfo()
+    check(lib().rsx_sort_lex_device(arr, len(cols), n, idx_out.data_ptr(), idx_out.element_size(), _stream_ptr(stream), C.byref(info)))
+    return idx_out[:n], info
+
+
 HINT_EVEN_TOP_DIGITS = 1
 
 
@@ -513,6 +582,19 @@ def radix_sort_topk_host(src, k, dtype, order=ASCENDING, want_idx=True, idx_dtyp
     check(lib().rsx_sort_topk(src.ctypes.data, src.size, k, dtype, order, keys.ctypes.data, None if idx is None else idx.ctypes.data,
                               4 if idx is None else idx.itemsize, C.byref(info)))
     return keys, idx, info
+
+
+def radix_sort_lex_host(cols, dtypes, orders=None, idx_dtype=None):
+    """rsx_sort_lex on host numpy columns (``cols[0]`` the most significant); returns (idx, info).  ``idx_dtype``: a 4- or
+    8-byte numpy integer type; default uint32 when n < 2^32, otherwise uint64."""
+    import numpy as np
+    cols = list(cols)
+    n = cols[0].size if cols else 0
+    idx = np.empty(n, dtype=idx_dtype if idx_dtype is not None else (np.uint32 if n < 2 ** 32 else np.uint64))
+    arr = _lex_cols([a.ctypes.data for a in cols], list(dtypes), orders)
+    info = LexInfo()
+    check(lib().rsx_sort_lex(arr, len(cols), n, idx.ctypes.data, idx.itemsize, C.byref(info)))
+    return idx, info
 
 
 def radix_sort_multi_host(src, aux, dtype, order=ASCENDING, devices=None):
