@@ -96,6 +96,14 @@ def count_matrix(hists, lut, world):
     return m
 
 
+# The exchange's two sizes in bytes (round 6: a piece of 2^31 bytes did not arrive whole).  A piece is what one rank sends another.
+# Pieces stay whole while the largest of the count matrix is below WHOLE_PIECE_MAX; from there on every piece goes in parts of at most
+# PIECE_LIMIT bytes.  Both are read when distributed_sort runs: tests lower them to reach the part-cutting code with small shards.
+PIECE_LIMIT = 1 << 30
+WHOLE_PIECE_MAX = 1 << 31
+
+EVEN_FACTOR = 1.2        # bins_are_even: the most a bin may hold, in means (a level-1 slot of the local sort holds 1.25)
+
 HEAVY_FACTOR = 1.25      # a digit holding more than this many fair shares (total / world) is split by the next byte too
 
 
@@ -117,6 +125,16 @@ def heavy_bins(share, world, bytes_left):
     if bytes_left <= 0 or world < 2 or total == 0:
         return []
     return [int(i) for i in np.nonzero(share > HEAVY_FACTOR * total / world)[0]]
+
+
+def bins_are_even(counts, levels):
+    """May the local sort of the received bins `counts` (global counts, exact) be told RSX_HINT_EVEN_TOP_DIGITS?
+
+    The hint switches off the level-1 test of the sample of a sort without a histogram, and that sort's level-1 slots hold 1.25
+    times the mean (slot_cap_for in csrc/rsx.hip): a bin above that loses the attempt after a full pass, for certain.  So: no bin
+    above EVEN_FACTOR = 1.2 means, at least two bins, and nothing refined (`levels` = 0: refined bins are not digits of one byte)."""
+    c = np.asarray(counts, dtype=np.float64)
+    return bool(levels == 0 and c.size >= 2 and float(c.max()) <= EVEN_FACTOR * float(c.mean()))
 
 
 class HipEngine:
@@ -163,7 +181,7 @@ class HipEngine:
 
     def sort_inplace_async(self, buf, scratch, even=False):
         """Stable sort of buf in place (scratch: as many elements), only enqueued on the current stream.
-        even: the caller has counted the keys of buf by their top varying byte and found no digit with twice its share
+        even: the caller has counted the keys of buf by their top varying byte and found them even (bins_are_even)
         (rsx_sort_inplace_async_hint: what arrives here was put in order of that byte by the senders' split passes, piece by
         piece, and would look clustered to the sample of a sort without a histogram)."""
         radix_sort_inplace_async(buf, scratch, dtype=self.dtype, order=self.order, hints=1 if even else 0)
@@ -421,14 +439,12 @@ def distributed_sort(shard, engine, group=None, recv_capacity=None, scratch=None
 
     def local_sort(lo, hi, sel):
         """the received keys recv[lo:hi] -- the bins `sel` of the split, in pieces that are each in bin order -- sorted in place.
-        The engine is told when the gathered counts say those bins are even (no bin with 1.5 times the mean, nothing refined):
-        what a sample of the pieces cannot see (rsx_sort_inplace_async_hint)."""
+        The engine is told when the gathered counts say those bins are even (bins_are_even: no bin above 1.2 times the mean,
+        nothing refined): what a sample of the pieces cannot see (rsx_sort_inplace_async_hint)."""
         if hi - lo <= 1:
             return
         if getattr(engine, "takes_even_hint", False):
-            c = total_bins[sel]
-            even = levels == 0 and c.size >= 2 and float(c.max()) <= 1.5 * float(c.mean())
-            engine.sort_inplace_async(recv[lo:hi], aux[lo:hi], even=even)
+            engine.sort_inplace_async(recv[lo:hi], aux[lo:hi], even=bins_are_even(total_bins[sel], levels))
         else:
             engine.sort_inplace_async(recv[lo:hi], aux[lo:hi])
 
@@ -449,15 +465,17 @@ def distributed_sort(shard, engine, group=None, recv_capacity=None, scratch=None
     es = shard.element_size()
     xdt = {8: torch.int64, 4: torch.int32}.get(es, torch.uint8)      # (NCCL has no 16-bit integer type)
     xu = es // {torch.int64: 8, torch.int32: 4, torch.uint8: 1}[xdt]      # units per element
-    PIECE_LIMIT = 1 << 30      # bytes one send / receive may carry (see one_exchange)
 
     def one_exchange():
         # A piece of 2^31 bytes or more does not arrive whole: the one-rank forced exchange of bench.py's 2^29 four-byte keys (ONE
         # piece of 2 GiB, the rank to itself) delivered a part of it, whatever the unit of the counts, and the sort behind it put
         # out a sorted array of the wrong keys (found in round 6 by comparing with torch.sort; bench.py checks checksums since).
-        # Between G >= 2 ranks a piece is at most half a shard: bench.py's sizes stay below the limit.  Above it the pieces go in
-        # parts of at most 1 GiB: slices of the one piece in a one-rank group, grouped send / receive otherwise.
-        big = max(int(recv_counts.max()), int(send_counts.max())) * es >= (1 << 31)
+        # Between G >= 2 ranks a piece is at most half a shard: bench.py's sizes stay below the limit.  From WHOLE_PIECE_MAX bytes
+        # on the pieces go in parts of at most PIECE_LIMIT bytes: slices of the one piece in a one-rank group, grouped send /
+        # receive otherwise (a rank's own piece is copied, as in exchange() below).  `big` is decided from the WHOLE count
+        # matrix, which every rank holds, never from a rank's own row and column: a rank that sees no big piece itself must
+        # still post the parts its peers post, not an all_to_all_single against their sends and receives.
+        big = int(matrix.max()) * es >= WHOLE_PIECE_MAX
         if not big:
             dist.all_to_all_single(recv.view(xdt), part.view(xdt),
                                    output_split_sizes=[int(x) * xu for x in recv_counts],
@@ -476,6 +494,10 @@ def distributed_sort(shard, engine, group=None, recv_capacity=None, scratch=None
             step_elems = PIECE_LIMIT // es
             ops = []
             for p in range(world):
+                if p == rank and not force_exchange:
+                    if int(recv_counts[p]):
+                        rv[int(roffs1[p]) * xu:int(roffs1[p + 1]) * xu].copy_(pv[int(soffs[p]) * xu:int(soffs[p + 1]) * xu])
+                    continue
                 for a in range(0, int(send_counts[p]), step_elems):
                     b = min(a + step_elems, int(send_counts[p]))
                     ops.append(dist.P2POp(dist.isend, pv[(int(soffs[p]) + a) * xu:(int(soffs[p]) + b) * xu], p, group))

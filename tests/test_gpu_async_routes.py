@@ -420,3 +420,26 @@ def test_keys_an_msd_split_has_ordered_take_the_fast_route_with_the_callers_word
     rsa.radix_sort_inplace_async(buf, torch.empty_like(buf), dtype=rsa.U32, hints=rsa.HINT_EVEN_TOP_DIGITS)
     assert rsa.async_route() != 5
     assert np.array_equal(buf.cpu().numpy().view(np.uint32), ol.oracle_sort(b, ol.U32)[0])
+    if G != 1:
+        return
+    # a hint that is wrong by LITTLE: uniform keys, but one top digit holds 1.4 times its share.  Every level-2 slot of that digit
+    # still has room (its 256 slots of 512 keys get 358 keys each, give or take 19), so the sample of the lower levels passes; the
+    # digit's own level-1 slot holds 1.25 times the mean (slot_cap_for: 81920 keys for a mean of 65536) and 91750 keys arrive: only
+    # the slot's capacity calls the attempt off, after the pass.  (multi.bins_are_even grants the hint up to 1.2 times the mean for
+    # this reason.)  At 1.15 times its share -- 75366 keys -- the same digit fits and the sort takes route 5.
+    mean = n // 256
+    for share, fits in ((1.4, False), (1.15, True)):
+        c = ol.splitmix_fill(n, ol.U32, 47)
+        others = np.flatnonzero((c >> np.uint32(24)) != 0x77)
+        extra = others[::others.size // int((share - 1.0) * mean)][:int((share - 1.0) * mean)]      # taken from all over the array
+        c[extra] = (c[extra] & np.uint32(0x00FFFFFF)) | np.uint32(0x77000000)
+        counts = np.bincount((c >> np.uint32(24)).astype(np.int64), minlength=256)
+        assert abs(int(counts[0x77]) - share * mean) < 0.02 * mean and (counts[0x77] > 81920) == (not fits)
+        assert int(np.delete(counts, 0x77).max()) < 1.02 * mean
+        c = c[np.argsort(c >> np.uint32(24), kind="stable")]          # (as one piece of a split: in order of the top byte)
+        rsa.reload_env()
+        buf = to_dev(c)
+        rsa.radix_sort_inplace_async(buf, torch.empty_like(buf), dtype=rsa.U32, hints=rsa.HINT_EVEN_TOP_DIGITS)
+        route = rsa.async_route()
+        assert np.array_equal(buf.cpu().numpy().view(np.uint32), ol.oracle_sort(c, ol.U32)[0]), share
+        assert (route == 5) == fits, (share, route)

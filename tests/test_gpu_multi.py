@@ -216,6 +216,71 @@ def test_exchange_steps_over_rccl_in_a_one_rank_group():
     assert out.returncode == 0 and "self-exchange OK" in out.stdout, out.stdout + out.stderr
 
 
+_RCCL_LOWERED_LIMITS = r"""
+import os, sys
+from datetime import timedelta
+import numpy as np
+import torch
+import torch.distributed as dist
+sys.path.insert(0, sys.argv[1])
+sys.path.insert(0, os.path.join(sys.argv[1], "tests"))
+import oracle_lib as ol
+import radix_sorting_amd as rsa
+from radix_sorting_amd import multi
+torch.cuda.set_device(0)
+dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0), timeout=timedelta(seconds=120))
+multi.PIECE_LIMIT = 1 << 20
+multi.WHOLE_PIECE_MAX = 1 << 21
+multi.HipEngine(ol.U32).overlap_stream(None, True)      # (calibrated here, so that what is recorded below is the exchange alone)
+calls = {"a2a": 0, "ops": []}
+real_a2a, real_batch = dist.all_to_all_single, dist.batch_isend_irecv
+def a2a(*args, **kw):
+    calls["a2a"] += 1
+    return real_a2a(*args, **kw)
+def batch(ops):
+    calls["ops"] += [op.tensor.numel() * op.tensor.element_size() for op in ops]
+    return real_batch(ops)
+dist.all_to_all_single, dist.batch_isend_irecv = a2a, batch
+n = 777777
+for dt, carrier in ((ol.U32, np.int32), (ol.U64, np.int64), (ol.I16, np.int16), (ol.U8, np.int8)):
+    es = ol.DTYPE_SIZE[dt]
+    a = ol.splitmix_fill(n, dt, 31)
+    shard = torch.from_numpy(a.view(carrier).copy()).cuda()
+    want = ol.oracle_sort(a, dt)[0]
+    for chunks in (1, 4):
+        calls.update(a2a=0, ops=[])
+        res, stats = multi.distributed_sort(shard, multi.HipEngine(dt), force_exchange=True, chunks=chunks)
+        torch.cuda.synchronize()
+        assert stats["received"] == n and stats["sent"] == 0 and stats["chunks"] == chunks, stats
+        assert np.array_equal(res.cpu().numpy().view(ol.NP_BITS[dt]), want), (dt, chunks)
+        if chunks == 1:     # the one piece whole below 2 MiB, in slices of PIECE_LIMIT // es keys from there on
+            slices = -(-n // ((1 << 20) // es)) if n * es >= (1 << 21) else 1
+            assert calls["a2a"] == slices and not calls["ops"], (dt, calls["a2a"], slices)
+        else:               # sends and receives to the rank itself, none above PIECE_LIMIT, all the keys both ways
+            assert calls["a2a"] == 0 and calls["ops"] and max(calls["ops"]) <= 1 << 20, (dt, calls)
+            assert sum(calls["ops"]) == 2 * n * es, (dt, sum(calls["ops"]))
+            if n * es > chunks << 20:     # some sub-range's piece is over PIECE_LIMIT: more than one send and one receive
+                assert len(calls["ops"]) >= 2 * (chunks + 1), (dt, len(calls["ops"]))
+dist.barrier()
+dist.destroy_process_group()
+print("lowered limits OK")
+"""
+
+
+def test_exchange_in_parts_over_rccl_with_lowered_limits():
+    """multi.PIECE_LIMIT = 2^20 and multi.WHOLE_PIECE_MAX = 2^21 in a one-rank group: 777777 keys of 4 and 8 bytes are one piece
+    over the limit, which chunks = 1 sends in slices (the world == 1 branch of one_exchange) and the pipeline in parts of its
+    sub-ranges' pieces; keys of 2 and 1 bytes stay below it and go whole.  In seconds what test_a_piece_of_two_gib_arrives_whole
+    needs 24 GiB for; every result is the oracle's."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, "-c", _RCCL_LOWERED_LIMITS, root], capture_output=True, text=True, timeout=600,
+                         env=_one_rank_env())
+    assert out.returncode == 0 and "lowered limits OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+
+
 _RCCL_TWO_GIB_PIECE = r"""
 import os, sys
 import torch
@@ -417,6 +482,70 @@ def test_distributed_sort_over_rccl_with_real_ranks(tmp_path):
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr",
                           "127.0.0.1", "--master-port", "29547", str(script), root], capture_output=True, text=True, timeout=1200, env=env)
     assert out.returncode == 0 and "two-rank sort OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+
+
+_TWO_RANK_LOPSIDED = r"""
+import os, sys
+from datetime import timedelta
+import numpy as np
+import torch
+import torch.distributed as dist
+root = sys.argv[1]
+sys.path.insert(0, root); sys.path.insert(0, os.path.join(root, "tests"))
+import oracle_lib as ol
+import radix_sorting_amd as rsa
+from radix_sorting_amd import multi
+rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+assert world == 2
+torch.cuda.set_device(int(os.environ["LOCAL_RANK"]))
+dist.init_process_group("nccl", device_id=torch.device("cuda", int(os.environ["LOCAL_RANK"])), timeout=timedelta(seconds=120))
+# rank 0: 60000 keys below 2^31, rank 1: 20000 keys above -- rank 0 keeps two thirds of its shard, the largest piece by far
+n_per = [60000, 20000]
+whole = ol.splitmix_fill(sum(n_per), ol.U32, 61)
+whole[:60000] &= np.uint32(0x7FFFFFFF)
+whole[60000:] |= np.uint32(0x80000000)
+hists = np.stack([np.bincount((whole[:60000] >> np.uint32(24)).astype(np.int64), minlength=256),
+                  np.bincount((whole[60000:] >> np.uint32(24)).astype(np.int64), minlength=256)]).astype(np.uint64)
+matrix = multi.count_matrix(hists, multi.choose_splitters(hists.sum(axis=0), 2), 2)
+multi.PIECE_LIMIT = 48002                          # 12000 keys a part
+multi.WHOLE_PIECE_MAX = int(matrix[0, 0]) * 4      # rank 0's own piece reaches it, and nothing that rank 1 sends or receives does
+over = matrix * 4 >= multi.WHOLE_PIECE_MAX
+assert over.sum() == 1 and over[0, 0] and int(matrix[0, 1]) > 12000, matrix
+first = sum(n_per[:rank])
+shard = torch.from_numpy(whole[first:first + n_per[rank]].view(np.int32).copy()).cuda()
+want_all = ol.oracle_sort(whole, ol.U32)[0]
+ok = True
+for chunks in (1, 4):
+    res, stats = multi.distributed_sort(shard, multi.HipEngine(ol.U32), chunks=chunks)
+    torch.cuda.synchronize()
+    got = res.cpu().numpy().view(np.uint32)
+    start = int(matrix[:, :rank].sum())
+    ok = ok and got.size == int(matrix[:, rank].sum()) and np.array_equal(got, want_all[start:start + got.size])
+    ok = ok and [int(x) for x in stats["recv_counts"]] == [int(x) for x in matrix[:, rank]]
+flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device="cuda")
+dist.all_reduce(flag, op=dist.ReduceOp.MIN)
+dist.barrier()
+dist.destroy_process_group()
+if rank == 0:
+    print("lopsided sort OK" if int(flag.item()) else "lopsided sort FAILED")
+"""
+
+
+@needs_two
+def test_a_big_piece_only_one_rank_sees_over_rccl_with_real_ranks(tmp_path):
+    """Two ranks on two GPUs with lowered limits and lopsided shards: only rank 0's own piece reaches multi.WHOLE_PIECE_MAX.  Both
+    ranks must cut the pieces between them in the same parts (`big` comes from the whole count matrix; decided per rank, rank 0
+    posted sends in parts against rank 1's all_to_all_single).  chunks in (1, 4) against the oracle's slices."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = tmp_path / "two_rank_lopsided.py"
+    script.write_text(_TWO_RANK_LOPSIDED)
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
+                          "127.0.0.1", "--master-port", "29549", str(script), root], capture_output=True, text=True, timeout=1200, env=env)
+    assert out.returncode == 0 and "lopsided sort OK" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
 
 
 @needs_two
