@@ -308,6 +308,21 @@ size_t radix_sort_topk(const T *src, size_t n, size_t k, T *out, IdxType *idx = 
 	return k;
 }
 
+// Not in the reference's header (what its counting sort's prefix sums answer): the elements at the m positions ranks[0 .. m-1]
+// (0-based, any order, repeats allowed) of the stable sorted order of src, which is not written, into out (room for m), and
+// their positions in src into idx if given (room for m; equal keys in ascending index order, as radix_sort_rank orders
+// them): out[j] == src[idx[j]] is what a full sort would leave at position ranks[j].  Scalar T with basic_kdfs::kdf;
+// RSX_DESCENDING for the complemented order (rsx_sort_nth, which also reports n_less / n_equal per rank).
+template <typename T, typename IdxType = uint32_t>
+void radix_sort_nth(const T *src, size_t n, const uint64_t *ranks, size_t m, T *out, IdxType *idx = nullptr, rsx_order order = RSX_ASCENDING)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_nth takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_nth: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_nth(src, n, ranks, m, rsx_detail::dtype_of<T>(), order, out, idx, sizeof(IdxType), nullptr, nullptr, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_nth", rc);
+}
+
 // Not in the reference's header (its text's stability argument one level up): the stable argsort of n rows by several key
 // columns, none of which is written, into idx_out (room for n).  c0 is the MOST significant column, as in ORDER BY c0, c1, ...
 // (np.lexsort takes its keys in the reverse order); rows equal in every column come in ascending index order.  Scalar column

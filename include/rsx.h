@@ -60,6 +60,13 @@
  *   workgroup; the sort route keeps what rsx_sort_rank keeps (2 n indices and the rank sort's workspace).  All of it is
  *   freed by rsx_release / rsx_release_stream and never allocated inside a stream capture (the call refuses a capturing
  *   stream).  If an allocation of the select route fails the call takes the sort route.
+ *   rsx_sort_nth*: the select route keeps, in the (device, stream) context, a control block with its tables (the records of
+ *   up to 64 ranks, 64 x 256 eight-byte counts, one count per workgroup: about 140 KiB), a candidate buffer of
+ *   cap = n / 8 + 1024 (key, index) pairs plus the second buffers of their sort (keys only when no indices are wanted), and
+ *   per rank asked for 28 bytes (the rank, n_less, n_equal, its record); rsx_sort_nth on host buffers also the staged keys and
+ *   the m staged outputs; the sort route keeps what rsx_sort_rank keeps (2 n indices and the rank sort's workspace).  All of
+ *   it is freed by rsx_release / rsx_release_stream and never allocated inside a stream capture (the call refuses a capturing
+ *   stream).  If an allocation of the select route fails the call takes the sort route.
  *   rsx_sort_lex*: in the (device, stream) context, apart from what its inner rank and key + payload sorts keep: 3 n indices
  *   of idx_bytes (the permutation and the second buffers of its sorts) and, unless the call is one lone column, 2 n keys of
  *   the widest packed type (2, 4 or 8 bytes); rsx_sort_lex on host buffers also the staged columns and n indices.  Freed by
@@ -123,6 +130,8 @@
  *                           force that route with it, tools/unique_probe.py sweeps the cut-off);
  *   RSX_TOPK_FORCE=1        rsx_sort_topk*: the select route whenever n >= 2 and 0 < k <= n; =2: always the sort route
  *                           (tests run both and compare; tools/topk_probe.py times both);
+ *   RSX_NTH_FORCE=1         rsx_sort_nth*: the select route whenever n >= 2 and 1 <= distinct ranks <= RSX_NTH_MAX_SELECT_RANKS;
+ *                           =2: always the sort route (tests run both and compare; tools/nth_probe.py times both);
  *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
  *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
@@ -397,6 +406,62 @@ int rsx_sort_topk_device(const void *d_src, size_t n, size_t k, rsx_dtype dtype,
 /* host or device pointers, as rsx_sort (all of the same kind) */
 int rsx_sort_topk(const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_order order,
                   void *out_keys, void *out_idx, size_t idx_bytes, rsx_topk_info *info);
+
+/* ---- the elements at given ranks of the sorted order (what a counting sort's prefix sums answer: medians, quantiles, the
+ *      splitters of a balanced MSD split) -------------------------------------------------------------------------------- */
+
+/* The entries at m given positions of the stable sorted order, without sorting the rest.
+ *   - Result: let R be what rsx_sort_rank returns for the same keys, dtype and order -- a stable argsort: equal keys in
+ *     ascending index order, RSX_DESCENDING orders by the complemented KDF.  For every j < m: out_idx[j] = R[ranks[j]] and
+ *     out_keys[j] is the bit-exact image of src[out_idx[j]] (NaN payloads, -0.0); n_less[j] is the number of elements whose
+ *     derived key is below that key's, n_equal[j] the number whose derived key equals it, so
+ *     n_less[j] <= ranks[j] < n_less[j] + n_equal[j].
+ *   - ranks, n_less and n_equal are HOST memory in both forms (as `cols` is for rsx_sort_lex).  Ranks are 0-based, in any
+ *     order, and may repeat; the outputs are in the caller's order of ranks.  n_less and n_equal may be NULL, each on its own.
+ *   - Buffers: d_src is never written.  Each device output has room for exactly m elements and nothing past element m - 1 is
+ *     touched.  Either of out_keys / out_idx may be NULL, not both.  idx_bytes is 4 or 8; with 4, n must fit, or the call
+ *     fails with RSX_EINVAL "does not fit".
+ *   - Errors: a rank >= n: RSX_EINVAL "rank exceeds n", nothing written; bad dtype, order or idx_bytes, both outputs NULL,
+ *     ranks == NULL with m > 0: RSX_EINVAL.  m == 0: RSX_OK, nothing written, no device needed.  n == 1: rsx_sort_nth on host
+ *     pointers needs no device, rsx_sort_nth_device only for the stores.  Otherwise, without a GPU: RSX_ENODEVICE, nothing
+ *     written.  A capturing stream: RSX_EINVAL (the call waits for what the selection found).  A failed allocation of the
+ *     select route's buffers is not an error: the call takes the sort route.
+ *   - Blocking: as rsx_sort_topk_device -- the call may synchronise `stream`; the device outputs are valid for work ordered
+ *     after it on `stream`; *info and the two host arrays are complete on return.
+ * RSX_NTH_SELECT: the distinct ranks, sorted, are carried TOGETHER through histograms of the derived keys'
+ * bytes, most significant first: a level counts, for every active bucket (a distinct prefix that still holds a wanted rank; at
+ * most 64), the next byte of the elements in it, and every rank moves on to the digit that holds it.  As soon as the active
+ * buckets together hold at most cap = n / 8 + 1024 elements, those are moved to a candidate buffer in index order (a count and
+ * a write over the input), sorted by the ordinary stable key + payload sort, and every answer is read at its place.  Keys that
+ * occur more than about n / 8 times never fit: after the last byte the prefixes ARE the keys and n_less / n_equal are known,
+ * so a call that wants no indices is answered from them (from_prefix = 1), and one that does takes the sort route.
+ * input_reads <= key_bytes + 2 always; 3 for a few ranks of keys that spread over their top byte.  RSX_NTH_SORT is
+ * rsx_sort_rank_device on a workspace copy, the m entries read through the ranks (small n, more than
+ * RSX_NTH_MAX_SELECT_RANKS distinct ranks). */
+enum { RSX_NTH_TRIVIAL = 0,   /* m == 0, or n < 2                                          */
+       RSX_NTH_SELECT  = 1,   /* multi-rank MSD radix select, then a sort of the candidates */
+       RSX_NTH_SORT    = 2 }; /* the ordinary stable rank sort, m entries read              */
+enum { RSX_NTH_MAX_SELECT_RANKS = 64 };   /* more DISTINCT ranks than this: the sort route  */
+
+typedef struct rsx_nth_info {
+	uint32_t route;          /* RSX_NTH_*                                                   */
+	uint32_t key_bytes;
+	uint32_t input_reads;    /* SELECT: kernels that read all n keys of d_src; otherwise 0  */
+	uint32_t digit_passes;   /* SELECT: histogram levels made (1 .. key_bytes)              */
+	uint32_t active_buckets; /* SELECT: distinct buckets that held a wanted rank at the last level */
+	uint32_t from_prefix;    /* SELECT: 1 = answered from the digits alone, no candidates moved     */
+	uint64_t candidates;     /* SELECT: (key, index) pairs moved and sorted; otherwise 0    */
+} rsx_nth_info;
+
+int rsx_sort_nth_device(const void *d_src, size_t n, const uint64_t *ranks, size_t m,
+                        rsx_dtype dtype, rsx_order order,
+                        void *d_out_keys, void *d_out_idx, size_t idx_bytes,
+                        uint64_t *n_less, uint64_t *n_equal,
+                        void *stream, rsx_nth_info *info);
+/* host or device pointers for src / out_keys / out_idx, as rsx_sort (all of the same kind) */
+int rsx_sort_nth(const void *src, size_t n, const uint64_t *ranks, size_t m,
+                 rsx_dtype dtype, rsx_order order, void *out_keys, void *out_idx, size_t idx_bytes,
+                 uint64_t *n_less, uint64_t *n_equal, rsx_nth_info *info);
 
 /* ---- ordering by several key columns (the stability argument one level up: README.md, "this is only possible because
  *      the sort is stable") ------------------------------------------------------------------------------------------ */

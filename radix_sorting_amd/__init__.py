@@ -67,6 +67,17 @@ class TopkInfo(C.Structure):
                 ("n_less", C.c_uint64), ("n_equal", C.c_uint64), ("kth_key", C.c_uint64)]
 
 
+# rsx_nth_info.route
+NTH_TRIVIAL, NTH_SELECT, NTH_SORT = range(3)
+NTH_MAX_SELECT_RANKS = 64
+
+
+class NthInfo(C.Structure):
+    """rsx_nth_info: the route rsx_sort_nth* took and how far its selection had to go."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("input_reads", C.c_uint32), ("digit_passes", C.c_uint32),
+                ("active_buckets", C.c_uint32), ("from_prefix", C.c_uint32), ("candidates", C.c_uint64)]
+
+
 LEX_MAX_COLS = 16
 
 
@@ -95,6 +106,7 @@ _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
 _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 _PTINFO = C.POINTER(TopkInfo)
+_PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 ABI = [
     ("rsx_device_count", _I, []),
@@ -119,6 +131,8 @@ ABI = [
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
     ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
+    ("rsx_sort_nth_device", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _VP, _PNINFO]),
+    ("rsx_sort_nth", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _PNINFO]),
     ("rsx_sort_lex_device", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _VP, _PLINFO]),
     ("rsx_sort_lex", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _PLINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
@@ -333,6 +347,60 @@ def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=
                                      None if idx_out is None else idx_out.data_ptr(),
                                      4 if idx_out is None else idx_out.element_size(), _stream_ptr(stream), C.byref(info)))
     return keys_out[:k], (None if idx_out is None else idx_out[:k]), info
+
+
+def _nth_ranks(ranks, n):
+    """The rank list of radix_sort_nth* as a contiguous uint64 array plus the two host arrays the call fills."""
+    import numpy as np
+    r = np.asarray(ranks)
+    if r.ndim != 1:
+        raise RsxError("ranks must be a one-dimensional sequence")
+    if r.size and r.dtype.kind not in "iu":
+        raise RsxError("ranks must be integers")
+    if r.size and r.dtype.kind == "i" and int(r.min()) < 0:
+        raise RsxError("ranks must not be negative")
+    if r.size and int(r.max()) >= n:
+        raise RsxError("rank exceeds n (largest rank %d, n = %d)" % (int(r.max()), n))
+    r = np.ascontiguousarray(r, dtype=np.uint64)
+    return r, np.zeros(r.size, dtype=np.uint64), np.zeros(r.size, dtype=np.uint64)
+
+
+def _u64p(a):
+    return a.ctypes.data_as(_PU64)
+
+
+def radix_sort_nth(src, ranks, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
+    """rsx_sort_nth_device: the entries at the positions ``ranks`` (0-based, any order, repeats allowed) of the stable sorted
+    order of ``src``, which is not written.
+
+    Returns (keys, idx or None, n_less, n_equal, info): ``idx[j]`` is entry ``ranks[j]`` of radix_sort_rank's result and
+    ``keys[j]`` the bit-exact image of ``src[idx[j]]``; ``n_less`` / ``n_equal`` are numpy uint64 arrays: how many elements
+    order before that key and how many equal it.  Outputs of m elements are allocated when none are given: ``keys`` of src's
+    dtype, ``idx`` int32 when n < 2^31, otherwise int64 (``want_idx=False``: no indices)."""
+    import torch
+    _check_dev(src)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    n = src.numel()
+    r, n_less, n_equal = _nth_ranks(ranks, n)
+    m = r.size
+    if keys_out is None:
+        keys_out = torch.empty(m, dtype=src.dtype, device=src.device)
+    if idx_out is None and want_idx:
+        idx_out = torch.empty(m, dtype=torch.int32 if n < 2 ** 31 else torch.int64, device=src.device)
+    for t, what, size in ((keys_out, "keys_out", src.element_size()), (idx_out, "idx_out", None)):
+        if t is None:
+            continue
+        _check_dev(t)
+        if t.numel() < m or (size is not None and t.element_size() != size):
+            raise RsxError("%s must have room for one element of the right size per rank" % what)
+    info = NthInfo()
+    check(lib().rsx_sort_nth_device(src.data_ptr(), n, _u64p(r), m, code, order, keys_out.data_ptr(),
+                                    None if idx_out is None else idx_out.data_ptr(),
+                                    4 if idx_out is None else idx_out.element_size(), _u64p(n_less), _u64p(n_equal),
+                                    _stream_ptr(stream), C.byref(info)))
+    return keys_out[:m], (None if idx_out is None else idx_out[:m]), n_less, n_equal, info
 
 
 def _lex_cols(ptrs, codes, orders):
@@ -582,6 +650,24 @@ def radix_sort_topk_host(src, k, dtype, order=ASCENDING, want_idx=True, idx_dtyp
     check(lib().rsx_sort_topk(src.ctypes.data, src.size, k, dtype, order, keys.ctypes.data, None if idx is None else idx.ctypes.data,
                               4 if idx is None else idx.itemsize, C.byref(info)))
     return keys, idx, info
+
+
+def radix_sort_nth_host(src, ranks, dtype, order=ASCENDING, want_idx=True, idx_dtype=None):
+    """rsx_sort_nth on a host numpy buffer; returns (keys, idx or None, n_less, n_equal, info) as radix_sort_nth does
+    (``idx_dtype``: a 4- or 8-byte numpy integer type; default uint32 when n < 2^32, otherwise uint64)."""
+    import numpy as np
+    if src.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src does not match the key type")
+    r, n_less, n_equal = _nth_ranks(ranks, src.size)
+    keys = np.empty(r.size, dtype=src.dtype)
+    idx = None
+    if want_idx:
+        idx = np.empty(r.size, dtype=idx_dtype if idx_dtype is not None else (np.uint32 if src.size < 2 ** 32 else np.uint64))
+    info = NthInfo()
+    check(lib().rsx_sort_nth(src.ctypes.data, src.size, _u64p(r), r.size, dtype, order, keys.ctypes.data,
+                             None if idx is None else idx.ctypes.data, 4 if idx is None else idx.itemsize, _u64p(n_less),
+                             _u64p(n_equal), C.byref(info)))
+    return keys, idx, n_less, n_equal, info
 
 
 def radix_sort_lex_host(cols, dtypes, orders=None, idx_dtype=None):
