@@ -1947,7 +1947,7 @@ int sort_keys_two_level(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, cons
 // For the arrays a two-level sort is for (hybrid_caps: cap2), blocking keys-only sorts.  *done = 1: sorted, *result set.
 // *done = 0: called off (the sample did not prove what it has to, or a slot overflowed) -- `src` and `aux` are untouched and
 // the caller runs the ordinary path.  A context that has been called off skips the next attempts of its kind (1, 3, 7 ... 31 sorts).
-template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_);
+template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_, bool counted_too = false);
 // kinds of sorts that learn separately: 0 / 1 keys only (4- / 8-byte keys), 2 rank sorts, 3 key + payload sorts
 template <typename KT> constexpr int blind_kind(size_t payload_bytes, bool rank = false)
 {
@@ -2801,7 +2801,7 @@ int sort_pairs_inplace_async(Ctx &c, KT *k, KT *ks, VT *v, VT *vs, size_t n, int
 }
 
 // ---- two MSB passes and leaves for key + payload sorts and rank sorts (4-byte keys, 4-byte payloads; rsx_leaf_pairs_kernel) ----
-template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_)
+template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_, bool counted_too)
 {
 	HybCaps caps{0, 0, 0, 0};
 	if (sizeof(KT) != 4 || val_bytes_ != 4 || !hybrid_enabled())
@@ -2809,8 +2809,9 @@ template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_)
 	// one level where every bucket of the highest kept column fits the pairs' leaf (5120 pairs: up to about a million pairs)
 	caps.cap1 = 5120;
 	caps.min_cols1 = 3;
-	// two levels: the slack route only, and only where a slot fits the pairs' leaf shape: 2^27 .. 2^28 pairs (cfg 4)
-	if (!env().no_slack && n >= ((size_t)1 << env().two_level_min_log2) && n <= ((size_t)1 << 28)) {
+	// two levels: the slack route, and only where a slot fits the pairs' leaf shape: 2^27 .. 2^28 pairs (cfg 4); key + payload
+	// sorts (counted_too) with RSX_NO_SLACK=1: the second pass counted first, as for keys alone (pairs_two_level)
+	if ((!env().no_slack || counted_too) && n >= ((size_t)1 << env().two_level_min_log2) && n <= ((size_t)1 << 28)) {
 		caps.cap2 = (u32)LeafShapes<KT>::Small::CAP;
 		caps.min_cols2 = 4;
 	}
@@ -2820,8 +2821,13 @@ template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_)
 // Pass 1 (by the highest kept column) has written (k1, v1).  The second pass goes into slots, the leaves write the payloads
 // (and the keys, if kfinal) to (kfinal, vfinal).  *ok = false: a slot overflowed -- nothing the caller owns was written, it
 // sorts with one pass per column.
+// RSX_NO_SLACK=1 (key + payload sorts only: kdense / vdense are their first buffers, which pass 1 has read): the counted second
+// pass of sort_keys_two_level -- the level-2 column counted per bucket (rsx_seg_hist1_kernel), the pass (k1, v1) -> (kdense,
+// vdense) at those offsets, the leaves on the dense buckets.  *ok = false: a (digit, digit) bucket does not fit the pairs' leaf --
+// known before the pass is enqueued, nothing but (k1, v1) has been written.
 template <typename KT, typename VT>
-int pairs_two_level(Ctx &c, const KT *k1, const VT *v1, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, bool *ok)
+int pairs_two_level(Ctx &c, const KT *k1, const VT *v1, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, bool *ok,
+                    KT *kdense = nullptr, VT *vdense = nullptr)
 {
 	typedef Sc2Cfg<KT, VT> C2;
 	typedef LeafCfg<u32, 4, 20, 3> L;   // 5120 pairs: the slack slot of 2^28 pairs; three workgroups per CU
@@ -2839,6 +2845,56 @@ int pairs_two_level(Ctx &c, const KT *k1, const VT *v1, KT *kfinal, VT *vfinal, 
 		RSX_TRY(c.seg.ensure(c.seg_btile_off + 257 * sizeof(u32)));
 		if (c.seg.p != before)
 			HIP_TRY(hipMemsetAsync(c.seg.p, 0, 256, c.stream));
+	}
+	if (env().no_slack) {
+		if (!kdense || !vdense || !kfinal)
+			return RSX_OK;
+		SegCtl *ctl = (SegCtl *)c.seg.p;
+		u32 *seghist = (u32 *)((char *)c.seg.p + c.seg_hist_off);
+		SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
+		LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
+		u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
+		if (!c.seg_ev)
+			HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
+		c.host_segctl->mode = SEG_MODE_NONE;
+		HIP_TRY(hipMemsetAsync(c.seg.p, 0, c.seg_status_off + st_bytes, c.stream));
+		hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
+		                   (u32)C2::TILE, tiles, ctl, btile);
+		{
+			ProfScope prof(0, (u64)n * sizeof(KT), c.stream);
+			hipLaunchKernelGGL((rsx_seg_hist1_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, k1, (const SegTile *)tiles, (const SegCtl *)ctl,
+			                   (const Plan *)c.plan(), ka, seghist);
+		}
+		hipLaunchKernelGGL((rsx_seg_plan_kernel<KT>), dim3(256), dim3(256), 0, c.stream, seghist, (const u64 *)c.ghist(), (u64)n,
+		                   (const Plan *)c.plan(), ctl, segtab, (u32)L::CAP, c.dev_host_segctl, 0u);
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
+		HIP_TRY(hipEventSynchronize(c.seg_ev));
+		if (c.host_segctl->mode != SEG_MODE_LEAVES)
+			return RSX_OK;
+		char *base = (char *)c.seg.p + c.seg_status_off;
+		SegArgs sa{};
+		sa.ctl = ctl;
+		sa.hist = (const u32 *)seghist;
+		sa.tiles = tiles;
+		sa.slots = (u32)sizeof(KT) - 1;
+		sa.overflow = &ctl->overflow;
+		{
+			ProfScope prof(1, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
+			hipLaunchKernelGGL((rsx_scatter2_kernel<KT, VT, u32, C2, false, DIG_GENERIC, false, KT, true>), dim3((unsigned)rows),
+			                   dim3(C2::BLOCK), 0, c.stream, k1, kdense, v1, vdense, (u64)n, 0u, (const u64 *)c.ghist(), 1u,
+			                   (u32 *)(base + 256), (u32 *)base, ka, (u32)SCATTER_SEG_LEAVES, (u64 *)nullptr, (const Plan *)c.plan(), 0u, 0u,
+			                   (const u32 *)nullptr, sa);
+		}
+		{
+			ProfScope prof(2, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
+			hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L>), dim3(env().leaf_grid), dim3(L::BLOCK), 0, c.stream, (const KT *)kdense,
+			                   (const VT *)vdense, 0u, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab, (const SegCtl *)ctl,
+			                   ka);
+		}
+		HIP_TRY(hipGetLastError());
+		*ok = true;
+		return RSX_OK;
 	}
 	const u32 mean = (u32)(n >> 16);
 	const u32 cap = slot_cap_for(mean);
@@ -3192,7 +3248,7 @@ int sort_pairs_device_impl(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int
 		}
 	}
 	Plan plan;
-	RSX_TRY(plan_phase<KT>(c, k0, n, ka, &plan, 0, (c.fast && !capture_armed() && !verify_mode()) ? hybrid_caps_pairs<KT>(n, sizeof(VT)) : HybCaps{0, 0, 0, 0}));
+	RSX_TRY(plan_phase<KT>(c, k0, n, ka, &plan, 0, (c.fast && !capture_armed() && !verify_mode()) ? hybrid_caps_pairs<KT>(n, sizeof(VT), true) : HybCaps{0, 0, 0, 0}));
 	info_from_plan(info, plan);
 	RSX_TRY(capture_hist(c, n, sizeof(KT)));
 	if (plan.sorted) {
@@ -3217,15 +3273,17 @@ int sort_pairs_device_impl(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int
 		}
 		if (plan.hyb == HYB_TWO_LEVEL) {
 			// two MSB passes (the second into slots) and leaves; on a slot's overflow: one pass per column, from (k0, v0) again
+			// (RSX_NO_SLACK=1: the second pass counted first and written to (k0, v0), which pass 1 has read; a bucket too large
+			// for the leaves is known before that pass)
 			const u32 top = plan.cols[plan.ncols - 1];
 			RSX_TRY((scatter_pass<KT, VT>(c, k0, k1, v0, v1, n, 8 * top, c.ghist() + 256 * top, ka, 0u)));
 			const bool in_aux = (plan.ncols & 1) != 0;
 			bool ok = false;
-			RSX_TRY((pairs_two_level<KT, VT>(c, k1, v1, in_aux ? k1 : k0, in_aux ? v1 : v0, n, ka, &ok)));
+			RSX_TRY((pairs_two_level<KT, VT>(c, k1, v1, in_aux ? k1 : k0, in_aux ? v1 : v0, n, ka, &ok, k0, v0)));
 			if (ok) {
 				if (info) {
 					info->result_in_aux = in_aux;
-					info->hybrid = 4;
+					info->hybrid = env().no_slack ? 2 : 4;
 				}
 				return RSX_OK;
 			}

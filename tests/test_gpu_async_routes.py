@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import pairs_lib as pl
 import radix_sorting_amd as rsa
 
 pytestmark = pytest.mark.gpu
@@ -205,6 +206,9 @@ def test_ranks_and_pairs_without_histogram_on_the_device(n):
     # the sign, so all four columns are kept; no byte scheme takes a column with two values, but the RANK sort packs the 24
     # varying bits -- SegCtl::compact, round 5 -- and stays on route 5; the pair sort wants its keys back and does not)
     cases = (("uniform, ties", twice, 5, 5), ("dominant top digit", half, 0, 0), ("constant column", const_col, 5, 0))
+    # payloads that are nothing like the ranks -- pairs_lib's `random` family --, expected by gathering through the ranks: a route
+    # that wrote the index where the payload belongs would pass with arange(n)
+    hv = pl.payloads("random", n, 4, 7500)
     for name, a, want_route, want_pair_route in (cases if n < (1 << 25) else cases[:2]):
         a = np.ascontiguousarray(a)
         want, _ = ol.want_ranks(a, ol.F32, big=1 << 22)
@@ -216,12 +220,12 @@ def test_ranks_and_pairs_without_histogram_on_the_device(n):
         assert np.array_equal(bits.cpu().numpy().view(np.uint32), a.view(np.uint32)), name      # the keys are only read
         assert np.array_equal(ranks.cpu().numpy().view(np.uint32), want), (name, "ranks")
         del ib, ranks
-        vals = torch.arange(n, dtype=torch.int32, device="cuda")
+        vals = torch.from_numpy(hv.view(np.int32)).cuda()
         ks, vs = torch.empty_like(bits), torch.empty_like(vals)
         rsa.radix_sort_pairs_inplace_async(bits, ks, vals, vs, dtype=rsa.F32)
         route = rsa.async_route()
         assert route == want_pair_route, (name, "pairs", route)
-        assert np.array_equal(vals.cpu().numpy().view(np.uint32), want), (name, "pairs")
+        assert np.array_equal(vals.cpu().numpy().view(np.uint32), hv[want]), (name, "pairs")
         assert np.array_equal(bits.cpu().numpy().view(np.uint32), a.view(np.uint32)[want]), (name, "pairs' keys")
         del vals, ks, vs, bits
 

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib as ol
+import pairs_lib as pl
 import radix_sorting_amd as rsa
 
 pytestmark = pytest.mark.gpu
@@ -421,12 +422,15 @@ def _ranks_and_pairs(a, want_route, what):
     assert np.array_equal(bits.cpu().numpy().view(np.uint32), a.view(np.uint32)), what      # (a rank sort leaves its keys alone)
     del ib, ranks
     rsa.reload_env()
-    vals = torch.arange(n, dtype=torch.int32, device="cuda")
+    # (payloads that are nothing like the ranks above -- pairs_lib's `random` family --, expected by gathering through them: a route
+    # that wrote the index where the payload belongs would pass with arange(n))
+    hv = pl.payloads("random", n, 4, n % 9973)
+    vals = torch.from_numpy(hv.view(np.int32)).cuda()
     ka, va = torch.empty_like(bits), torch.empty_like(vals)
     kr, vr, info = rsa.radix_sort_pairs(bits, ka, vals, va, dtype=rsa.F32)
     torch.cuda.synchronize()
     assert (info.hybrid == 5) if want_route == 5 else (info.hybrid != 5), (what, info.hybrid)
-    assert np.array_equal(vr.cpu().numpy().view(np.uint32), want), what
+    assert np.array_equal(vr.cpu().numpy().view(np.uint32), hv[want]), what
     assert np.array_equal(kr.cpu().numpy().view(np.uint32), a.view(np.uint32)[want]), what
 
 
