@@ -39,815 +39,10 @@
 
 using namespace rsx;
 
+#include "rsx_env.hpp"   // the RSX_* switches
+#include "rsx_ctx.hpp"   // the error convention, DevBuf, Ctx, profiling, get_ctx
+
 namespace {
-
-thread_local char g_err[512] = "";
-
-int fail(int code, const char *fmt, ...)
-{
-	va_list ap;
-	va_start(ap, fmt);
-	vsnprintf(g_err, sizeof(g_err), fmt, ap);
-	va_end(ap);
-	return code;
-}
-
-#define HIP_TRY(expr)                                                                              \
-	do {                                                                                           \
-		hipError_t e_ = (expr);                                                                    \
-		if (e_ != hipSuccess) {                                                                    \
-			(void)hipGetLastError();                                                               \
-			return fail(e_ == hipErrorOutOfMemory ? RSX_ENOMEM : RSX_EHIP, "%s failed: %s (%s:%d)", #expr, \
-			            hipGetErrorString(e_), __FILE__, __LINE__);                                \
-		}                                                                                          \
-	} while (0)
-
-#define RSX_TRY(expr)          \
-	do {                       \
-		int rc_ = (expr);      \
-		if (rc_ != RSX_OK)     \
-			return rc_;        \
-	} while (0)
-
-size_t dtype_size(int dtype)
-{
-	switch (dtype) {
-	case RSX_U8: case RSX_I8: return 1;
-	case RSX_U16: case RSX_I16: return 2;
-	case RSX_U32: case RSX_I32: case RSX_F32: return 4;
-	case RSX_U64: case RSX_I64: case RSX_F64: return 8;
-	default: return 0;
-	}
-}
-
-template <typename KT>
-KdfArgs<KT> make_kdf(int dtype, int order)
-{
-	KdfArgs<KT> a;
-	const KT high = (KT)((KT)1 << (sizeof(KT) * 8 - 1));
-	const bool is_signed = dtype == RSX_I8 || dtype == RSX_I16 || dtype == RSX_I32 || dtype == RSX_I64;
-	const bool is_float = dtype == RSX_F32 || dtype == RSX_F64;
-	a.fmask = is_float ? (KT)~(KT)0 : (KT)0;
-	a.sflip = (is_signed || is_float) ? high : (KT)0;
-	a.desc = order == RSX_DESCENDING ? (KT)~(KT)0 : (KT)0;
-	return a;
-}
-
-// ---- the RSX_* switches of the environment, read ONCE per process (rsx_reload_env() reads them again: tests) ----------------
-// "set" switches are on when the variable exists, "=1" switches when its value starts with '1' (as documented in rsx.h).
-std::atomic<u32> g_env_epoch{0};   // bumped by rsx_reload_env()
-// rsx_sort_unique*: the widest bitmap the library was compiled for, and the widest it takes by default
-enum : unsigned { UNIQUE_MAX_BITS_COMPILED = 30, UNIQUE_MAX_BITS_DEFAULT = 24 };
-// rsx_sort_lex*: neighbouring columns are packed into one key of at most this many bytes
-enum : unsigned { LEX_PACK_BYTES_DEFAULT = 4 };
-struct Env {
-	bool host_register = false;      // RSX_HOST_REGISTER=1
-	bool force_table_rank = false;   // RSX_FORCE_TABLE_RANK=1
-	bool verify = false;             // RSX_VERIFY=1
-	bool verify_whole = false;       // RSX_VERIFY=2: keys-only sorts check their whole result (sortedness + checksums), any route
-	bool verify_inject = false;      // RSX_VERIFY_INJECT (set)
-	bool no_hot = false;             // RSX_NO_HOT (set)
-	bool elem_loads = false;         // RSX_ELEM_LOADS=1
-	bool no_small_tiles = false;     // RSX_NO_SMALL_TILES (set)
-	bool no_hybrid = false;          // RSX_NO_HYBRID=1
-	bool no_small_sort = false;      // RSX_NO_SMALL_SORT (set)
-	bool no_fill_runs = false;       // RSX_NO_FILL_RUNS (set)
-	bool no_speculation = false;     // RSX_NO_SPECULATION (set)
-	bool compact_bits = false;       // RSX_COMPACT_BITS=1
-	bool no_narrow_keys = false;     // RSX_NO_NARROW_KEYS (set)
-	bool no_host_small = false;      // RSX_NO_HOST_SMALL (set)
-	bool no_fused_hist = false;      // RSX_NO_FUSED_HIST=1
-	bool no_slack = false;           // RSX_NO_SLACK=1
-	bool no_self_plan = false;       // RSX_NO_SELF_PLAN=1
-	bool no_blind = false;           // RSX_NO_BLIND=1: every sort starts with the histogram
-	unsigned blind_min_log2 = 0;     // RSX_BLIND_MIN_LOG2: keys-only sorts may skip the histogram from 2^this keys on (0: the measured floors)
-	bool no_leaf_prefix = false;     // RSX_NO_LEAF_PREFIX=1: leaves of 8-byte keys sort by every column they have left (rsx_hybrid.hpp)
-	bool no_leaf16w2k = false;       // RSX_NO_LEAF16W2K=1: slots of 1025 .. 2048 values take a 128-thread workgroup per leaf (rsx_leaf16_kernel) instead of a wave
-	bool no_leaf16q = false;         // RSX_NO_LEAF16Q=1: slots of up to 256 values take a wave per leaf (rsx_leaf16w_kernel) instead of a row of sixteen lanes
-	bool no_narrow_slots = false;    // RSX_NO_NARROW_SLOTS=1: the level-2 slots of 8-byte keys always hold whole keys (SegCtl::narrow)
-	bool no_aux_slots = false;       // RSX_NO_AUX_SLOTS=1: the level-1 slots of a sort without a histogram all lie in scratch memory
-	bool no_narrow1 = false;         // RSX_NO_NARROW_LEVEL1=1: the level-1 pass of 8-byte keys always writes whole keys (SegCtl::narrow stays below 2)
-	bool no_dense_slots = false;     // RSX_NO_DENSE_SLOTS=1: the level-2 pass of a sort without a histogram writes whole keys
-	bool force_dense_slots = false;  // RSX_DENSE_SLOTS=1: (kept for old scripts: two-byte slots are now written for every slot size rsx_leaf16_kernel takes)
-	bool no_unstable = false;        // RSX_NO_UNSTABLE=1: the MSB passes of a sort without a histogram rank per wave (stable), as every other pass
-	bool no_shift = false;           // RSX_NO_SHIFT=1: the MSB digits of a sort without a histogram are whole bytes (the two highest kept columns) always
-	bool no_pass16 = false;          // RSX_NO_PASS16=1: the level-2 pass into two-byte slots is rsx_scatter2_kernel<..., KTO = u16, SEG> as in round 4 (rsx_pass16.hpp)
-	unsigned pass16_wgs = 2;         // RSX_PASS16_WGS=1: ... one workgroup per CU (probe)
-	bool no_packed_keys = false;     // RSX_NO_PACKED_KEYS=1: rank sorts without a histogram go by byte columns only (SegCtl::compact never set)
-	bool no_pass32a = false;         // RSX_NO_PASS32A=1: the level-1 pass of such a sort is rsx_scatter2_kernel<..., SEG> with its look-back chain (rsx_pass32.hpp)
-	unsigned pass32_min_mi = 0;      // RSX_PASS32_MIN_MI=k (probe): the level-1 atom pass from k Mi keys on (default: 52 Mi 4-byte keys, 24 Mi 8-byte keys)
-	int pass32_prefetch = -1;        // RSX_PASS32_PREFETCH=0|1 (probe): rsx_pass32a_kernel requests a tile's keys while it writes the tile before (1) or when it starts on the tile (0, the default)
-	bool no_pass16a = false;         // RSX_NO_PASS16A=1: ... whose runs are ragged (rsx_pass16_kernel) instead of whole 64-byte atoms (rsx_pass16a_kernel)
-	unsigned pass16_dbg = 0;         // RSX_PASS16_DBG=1|2 (probe, WRONG OUTPUT): no stores / only whole aligned 64-byte atoms stored
-	bool no_leafc = false;           // RSX_NO_LEAFC=1: no two-byte slots of more than 5120 values (rsx_leafc.hpp): sorts without a histogram of 4-byte keys end below 2^30 keys and their larger leaves sort whole keys, as in round 4
-	unsigned force_leafc = 0;        // RSX_FORCE_LEAFC=1..6 (tests): two-byte slots of ANY size take the leaves of the large ones -- 1 the counting leaves at once, 2 / 3 / 4 / 5 / 6 rsx_leaf16_kernel's 10240- / 20480- / 6144- / 7680- / 15360-value shape and the counting leaves behind it
-	bool no_leaf16 = false;          // RSX_NO_LEAF16=1: two-byte slots are sorted by rsx_leaf_sort_kernel (two LDS passes) as in round 3
-	unsigned leaf16_maxbin = 25;     // RSX_LEAF16_MAXBIN (tests): leaves with a fuller bin go to rsx_leaf_sort_kernel (0: every leaf)
-	unsigned leaf_grid = 65536;      // RSX_LEAF_GRID (probe): workgroups of a level-2 leaf launch (65536: one per table entry)
-	unsigned two_level_min_log2 = 27; // RSX_TWO_LEVEL_MIN_LOG2: two MSB passes + leaves from 2^this keys on (tests: 22)
-	bool no_odd_stride = false;      // RSX_NO_ODD_STRIDE=1: the level-1 slots of a sort without a histogram lie 1.25 means apart, rounded to 1 KiB, as in round 5
-	unsigned cap1_pad_kib = 0;       // RSX_CAP1_PAD_KIB=k (probe): k KiB more per level-1 slot of a sort without a histogram
-	unsigned probe = 0;              // RSX_PROBE=bits (measurements; results stay right): 1 the leaf table of a sort without a histogram in reverse slot order, 4 every device-scheduled sort as if hinted (rsx_sort_inplace_async_hint)
-	bool no_pass64a = false;         // RSX_NO_PASS64A=1: the level-2 pass of 8-byte keys into four-byte slots is the chained rsx_scatter2_kernel of round 4 (rsx_pass64.hpp)
-	bool no_log = false;             // RSX_NO_LOG=1: 8-byte keys never take the (bit length, mantissa) digits of rsx_logroute.hpp (rsx_info.hybrid never 6)
-	bool log_leaf_big = false;       // RSX_LOG_LEAF_BIG=1 (tests): that route's leaves in the shape for 10240 values at every size
-	bool pairs_leaf_big = false;     // RSX_PAIRS_LEAF_BIG=1 (tests): key + payload and rank sorts without a histogram: the leaves' shape for 10240 pairs at every size
-	unsigned log_min_log2 = 0;       // RSX_LOG_MIN_LOG2: ... from 2^this keys on (tests: 20; default: from 24 Mi keys)
-	unsigned unique_max_bits = UNIQUE_MAX_BITS_DEFAULT;   // RSX_UNIQUE_MAX_BITS=k: rsx_sort_unique*: the widest bitmap is 2^k bits (0: never a bitmap or a table; at most 30)
-	unsigned nth_force = 0;          // RSX_NTH_FORCE=1: rsx_sort_nth* selects whenever n >= 2 and 1 <= distinct ranks <= 64; =2: always the sort route
-	unsigned topk_force = 0;         // RSX_TOPK_FORCE=1: rsx_sort_topk* selects whenever n >= 2 and 0 < k <= n; =2: always the sort route
-	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
-	void load()
-	{
-		auto is_set = [](const char *name) { return getenv(name) != nullptr; };
-		auto is_one = [](const char *name) {
-			const char *e = getenv(name);
-			return e && e[0] == '1';
-		};
-		host_register = is_one("RSX_HOST_REGISTER");
-		force_table_rank = is_one("RSX_FORCE_TABLE_RANK");
-		verify = is_one("RSX_VERIFY");
-		{
-			const char *e = getenv("RSX_VERIFY");
-			verify_whole = e && e[0] == '2';
-		}
-		verify_inject = is_set("RSX_VERIFY_INJECT");
-		no_hot = is_set("RSX_NO_HOT");
-		elem_loads = is_one("RSX_ELEM_LOADS");
-		no_small_tiles = is_set("RSX_NO_SMALL_TILES");
-		no_hybrid = is_one("RSX_NO_HYBRID");
-		no_small_sort = is_set("RSX_NO_SMALL_SORT");
-		no_fill_runs = is_set("RSX_NO_FILL_RUNS");
-		no_speculation = is_set("RSX_NO_SPECULATION");
-		compact_bits = is_one("RSX_COMPACT_BITS");
-		no_narrow_keys = is_set("RSX_NO_NARROW_KEYS");
-		no_host_small = is_set("RSX_NO_HOST_SMALL");
-		no_fused_hist = is_one("RSX_NO_FUSED_HIST");
-		no_slack = is_one("RSX_NO_SLACK");
-		no_self_plan = is_one("RSX_NO_SELF_PLAN");
-		no_blind = is_one("RSX_NO_BLIND");
-		blind_min_log2 = 0;
-		if (const char *e = getenv("RSX_BLIND_MIN_LOG2"))
-			blind_min_log2 = (unsigned)std::max(22, std::min(30, atoi(e)));
-		no_leaf_prefix = is_one("RSX_NO_LEAF_PREFIX");
-		no_leaf16q = is_one("RSX_NO_LEAF16Q");
-		no_narrow_slots = is_one("RSX_NO_NARROW_SLOTS");
-		no_aux_slots = is_one("RSX_NO_AUX_SLOTS");
-		no_narrow1 = is_one("RSX_NO_NARROW_LEVEL1");
-		no_dense_slots = is_one("RSX_NO_DENSE_SLOTS");
-		force_dense_slots = is_one("RSX_DENSE_SLOTS");
-		no_leaf16 = is_one("RSX_NO_LEAF16");
-		no_leafc = is_one("RSX_NO_LEAFC");
-		no_leaf16w2k = is_one("RSX_NO_LEAF16W2K");
-		if (const char *e = getenv("RSX_PASS32_MIN_MI"))
-			pass32_min_mi = (unsigned)atoi(e);
-		if (const char *e = getenv("RSX_PASS32_PREFETCH"))
-			pass32_prefetch = e[0] == '1' ? 1 : 0;
-		if (const char *e = getenv("RSX_FORCE_LEAFC"))
-			force_leafc = (unsigned)atoi(e);
-		no_pass16 = is_one("RSX_NO_PASS16");
-		no_pass16a = is_one("RSX_NO_PASS16A");
-		no_pass32a = is_one("RSX_NO_PASS32A");
-		no_packed_keys = is_one("RSX_NO_PACKED_KEYS");
-		pass16_wgs = 2;
-		if (const char *e = getenv("RSX_PASS16_WGS"))
-			pass16_wgs = atoi(e) == 1 ? 1u : 2u;
-		pass16_dbg = 0;
-		if (const char *e = getenv("RSX_PASS16_DBG"))
-			pass16_dbg = (unsigned)atoi(e);
-		no_shift = is_one("RSX_NO_SHIFT");
-		no_unstable = is_one("RSX_NO_UNSTABLE");
-		leaf16_maxbin = 25;
-		if (const char *e = getenv("RSX_LEAF16_MAXBIN"))
-			leaf16_maxbin = (unsigned)std::max(0, std::min(25, atoi(e)));
-		leaf_grid = 65536;
-		if (const char *e = getenv("RSX_LEAF_GRID"))
-			leaf_grid = std::max(256, std::min(65536, atoi(e)));
-		no_odd_stride = is_one("RSX_NO_ODD_STRIDE");
-		cap1_pad_kib = 0;
-		if (const char *e = getenv("RSX_CAP1_PAD_KIB"))
-			cap1_pad_kib = (unsigned)std::max(0, std::min(65536, atoi(e)));
-		probe = 0;
-		if (const char *e = getenv("RSX_PROBE"))
-			probe = (unsigned)atoi(e);
-		no_pass64a = is_one("RSX_NO_PASS64A");
-		no_log = is_one("RSX_NO_LOG");
-		log_leaf_big = is_one("RSX_LOG_LEAF_BIG");
-		pairs_leaf_big = is_one("RSX_PAIRS_LEAF_BIG");
-		log_min_log2 = 0;
-		if (const char *e = getenv("RSX_LOG_MIN_LOG2"))
-			log_min_log2 = (unsigned)std::max(20, std::min(29, atoi(e)));
-		topk_force = 0;
-		if (const char *e = getenv("RSX_TOPK_FORCE"))
-			topk_force = e[0] == '1' ? 1u : e[0] == '2' ? 2u : 0u;
-		nth_force = 0;
-		if (const char *e = getenv("RSX_NTH_FORCE"))
-			nth_force = e[0] == '1' ? 1u : e[0] == '2' ? 2u : 0u;
-		lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;
-		if (const char *e = getenv("RSX_LEX_PACK_BYTES")) {
-			const int v = atoi(e);
-			if (v >= 1 && v <= 8)
-				lex_pack_bytes = (unsigned)v;
-		}
-		unique_max_bits = UNIQUE_MAX_BITS_DEFAULT;
-		if (const char *e = getenv("RSX_UNIQUE_MAX_BITS"))
-			unique_max_bits = (unsigned)std::max(0, std::min((int)UNIQUE_MAX_BITS_COMPILED, atoi(e)));
-		two_level_min_log2 = 27;
-		if (const char *e = getenv("RSX_TWO_LEVEL_MIN_LOG2")) {
-			const int v = atoi(e);
-			if (v >= 22 && v <= 30)
-				two_level_min_log2 = (unsigned)v;
-		}
-	}
-};
-Env g_env;
-std::once_flag g_env_once;
-inline const Env &env()
-{
-	std::call_once(g_env_once, [] { g_env.load(); });
-	return g_env;
-}
-
-// ---- the *_inplace_async entry points (enqueue only; the stream may be capturing a graph) mark their extent ----------------
-// What the mark changes: a scratch buffer that would have to grow under a capture is an error instead of a hipFree / hipMalloc
-// (DevBuf::ensure), and no slot array is ever released from inside such a call (blind_enqueue, pairs_blind_enqueue): a graph
-// captured earlier on this context may still name it.
-thread_local bool g_in_async = false;
-thread_local hipStream_t g_async_stream = nullptr;
-struct AsyncScope {
-	bool prev;
-	hipStream_t prev_stream;
-	explicit AsyncScope(hipStream_t s) : prev(g_in_async), prev_stream(g_async_stream)
-	{
-		g_in_async = true;
-		g_async_stream = s;
-	}
-	~AsyncScope()
-	{
-		g_in_async = prev;
-		g_async_stream = prev_stream;
-	}
-	AsyncScope(const AsyncScope &) = delete;
-	AsyncScope &operator=(const AsyncScope &) = delete;
-};
-
-// ---- a growable device allocation -------------------------------------------
-struct DevBuf {
-	void *p = nullptr;
-	size_t cap = 0;
-	bool external = false;   // a slice of a caller-owned workspace (rsx_sort_inplace_async_ws): never grown, never freed
-	// Inside a *_inplace_async entry point (AsyncScope) the stream may be capturing: a buffer never grows under a capture -- the
-	// graph would keep the old address, and hipFree / hipMalloc are not capturable.
-	int ensure(size_t bytes)
-	{
-		if (bytes <= cap)
-			return RSX_OK;
-		if (external)
-			return fail(RSX_EINVAL, "the caller's workspace is too small: %zu bytes needed where %zu were set aside "
-			                        "(size it with rsx_workspace_bytes)", bytes, cap);
-		if (g_in_async) {
-			hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-			if (hipStreamIsCapturing(g_async_stream, &st) == hipSuccess && st != hipStreamCaptureStatusNone)
-				return fail(RSX_EINVAL, "a scratch buffer would have to grow (%zu -> %zu bytes) while the stream is capturing: run the "
-				                        "sort once outside the capture, or use the *_ws entry points with a workspace of your own",
-				            cap, bytes);
-			(void)hipGetLastError();
-		}
-		// A buffer that GROWS is rounded up to an eighth of the power of two below its size (buffers of 2 MiB and more; smaller
-		// ones get an eighth on top): a sort of slightly more keys than the last one -- the sub-ranges of a distributed sort, a
-		// growing table -- finds room instead of paying hipFree + hipMalloc, and hipFree synchronises the device.  At most
-		// 12.5 % above the request (round 4 gave GiB-sized slot arrays no headroom at all and re-allocated on every record
-		// size).  A buffer's FIRST allocation is what was asked for (to 2 MiB): the four slot arrays of 2^28 pairs, a tile
-		// above 1.25 GiB each, took 1.375 -- half a GiB for sorts that never come; sizes that do vary pay one re-allocation.
-		size_t want = bytes + bytes / 8;
-		if (!p && bytes >= ((size_t)2 << 20)) {
-			want = (bytes + ((size_t)2 << 20) - 1) & ~(((size_t)2 << 20) - 1);
-		} else if (bytes >= ((size_t)2 << 20)) {
-			size_t p2 = (size_t)1 << 21;
-			while ((p2 << 1) <= bytes)
-				p2 <<= 1;
-			const size_t step = p2 / 8;
-			want = (bytes + step - 1) / step * step;
-		}
-		// The new allocation is made BEFORE the old one goes: if it fails the old buffer (which a graph captured earlier may
-		// still name) stays where it is; only then the old one is given up to make room.
-		void *np = nullptr;
-		hipError_t e = hipMalloc(&np, want);
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			want = bytes;
-			e = hipMalloc(&np, want);
-		}
-		if (e != hipSuccess && p && !g_in_async) {
-			(void)hipGetLastError();
-			(void)hipFree(p);
-			p = nullptr;
-			cap = 0;
-			e = hipMalloc(&np, want);
-		}
-		if (e != hipSuccess) {
-			(void)hipGetLastError();
-			return fail(RSX_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
-		}
-		if (p)
-			(void)hipFree(p);
-		p = np;
-		cap = want;
-		return RSX_OK;
-	}
-	void release()
-	{
-		if (p && !external)
-			(void)hipFree(p);
-		p = nullptr;
-		cap = 0;
-	}
-	void borrow(void *ptr, size_t bytes)
-	{
-		p = ptr;
-		cap = bytes;
-		external = true;
-	}
-};
-
-// ---- per (device, stream) context --------------------------------------------
-struct Ctx {
-	int device = -1;
-	hipStream_t stream = nullptr;
-	// fixed small state: [unsorted u32 | hotd 9 u32 | plan_done | pad 64][Plan 64][kept 16 u32 64]
-	DevBuf small;
-	DevBuf hist;        // counts, then exclusive offsets [key bytes][256] u64
-	DevBuf hpart;       // the histogram kernel's per-workgroup rows [workgroups][key bytes][256] u32
-	DevBuf status;      // [ticket u32, pad to 256 B][tiles * 256 status words]
-	DevBuf keys[2];     // key ping-pong for rank sorts / host staging
-	DevBuf vals[2];     // payload ping-pong for host staging / narrow-index rank
-	DevBuf recs[2];     // record gather staging
-	DevBuf tkeys;       // keys extracted from records (rsx_sort_records_tagged*)
-	DevBuf ckeys;       // rank sorts: the keys' varying bits packed together (RSX_COMPACT_BITS)
-	DevBuf joint;       // 2-byte keys: [65536 u32 counts][65537 u64 offsets] of the 16-bit digit (rsx_joint16_kernel)
-	DevBuf seg;         // two-level sorts (rsx_hybrid.hpp): [SegCtl][per-bucket digit counts][status regions][leaf segments][tiles]
-	size_t seg_hist_off = 0, seg_status_off = 0, seg_segtab_off = 0, seg_tiles_off = 0, seg_btile_off = 0, seg_redo_off = 0;
-	SelfPlanArgs pass_sp{nullptr, nullptr, nullptr, nullptr, HybCaps{0, 0, 0, 0}};   // a self-planned pass 0 (SCATTER_SELF_PLAN)
-	DevBuf gscan;       // [256] u64: the highest kept column's offsets from a self-planned pass 0 (for the leaves)
-	// rsx_sort_inplace_async after an attempt without the histogram: the control block whose `mode` tells the histogram-first
-	// kernels enqueued behind it that there is nothing left to do
-	const SegCtl *pass_gate = nullptr;
-	bool async_tried_blind = false;   // ... whether the last rsx_sort_inplace_async of this context enqueued such an attempt
-	bool ws_blind = false;            // a context in a caller's workspace that has room for the slots of a sort without a histogram (borrow_ctx)
-	bool boff_forget = false;   // rsx_reload_env since the last attempt: SegCtl::boff_* are zeroed before the next one
-	u32 hints = 0;                    // what the caller of the sort being enqueued has said about its keys (rsx_sort_inplace_async_hint)
-	bool async_small = false;         // ... or was the one-launch sort of a small array (rsx_async_route: 0, whatever the device's words say)
-	const void *pass_alt = nullptr;   // rsx_sort_rank_inplace_async: the second work copy of the keys (SCATTER_RANK_ASYNC passes)
-	DevBuf vsum;        // RSX_VERIFY=2: [descents, sum, mix] of the input and of the result
-	DevBuf vasync;      // RSX_VERIFY: mismatches found in device-scheduled passes, kept until rsx_verify_poll / the next blocking sort
-	DevBuf slack_v;     // ... the payloads' slots (key + payload and rank sorts)
-	DevBuf slack;       // two-level sorts, slack attempt: 65536 slots of slack_cap keys (+ a tile of padding)
-	u32 slack_cap = 0;
-	u32 slack_mean = 0;   // the mean number of keys of a level-2 slot of the sort being enqueued (n / 65536: pass16a_wanted)
-	DevBuf slack1_v;    // ... and of as many payloads (pairs_blind)
-	DevBuf slack1;      // sorts without a histogram (sort_keys_blind): the level-1 pass's 256 slots of slack1_cap keys
-	DevBuf logb;        // rsx_logroute.hpp: [LogCtl][LogTabs][level-2 cursors 2 x 65536][level-2 tiles]
-	DevBuf logslots;    // ... the level-2 slots (four bytes per key)
-	DevBuf ubits;       // rsx_sort_unique*: the bitmap, one bit per packed value (at most 2^RSX_UNIQUE_MAX_BITS / 8 bytes)
-	DevBuf urecs;       // ... [8 u64: sample / totals][UniqueRec per chunk of the bitmap or tile of the sorted array]
-	DevBuf tkctl;       // rsx_sort_topk*: [TopkCtl][rows of the input's ranges][rows of the candidates'][their offsets]
-	DevBuf tkpairs;     // ... the k (key, index) pairs and the second buffers of their sort: [keys k][keys k][indices k][indices k]
-	DevBuf tkcand;      // ... the selected bucket's (key, index) candidates: [keys cap][indices cap], cap = n / 8 + 1024
-	DevBuf tkout;       // ... rsx_sort_topk on host buffers: the staged outputs
-	DevBuf nthctl;      // rsx_sort_nth*: [NthCtl][table: 64 buckets x 256 digits u64][counts of the input's ranges u64]
-	DevBuf nthcand;     // ... the active buckets' (key, index) candidates and the second buffers of their sort: [keys cap] x 2 [indices cap] x 2
-	DevBuf nthio;       // ... [ranks m u64][n_less m u64][n_equal m u64][record of each position m u32]
-	DevBuf nthout;      // ... rsx_sort_nth on host buffers: the staged outputs
-	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
-	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
-	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
-	LogCtl *host_logctl = nullptr;   // pinned: the control block as the device left it
-	hipEvent_t log_ev = nullptr;
-	u32 slack1_cap = 0;
-	u32 slack1_lo = 0;  // ... of which the first slack1_lo lie in the caller's second buffer (keys-only sorts; 0: all in slack1)
-	bool narrow1 = false;   // 8-byte keys: the forms that keep low words in the level-1 slots are enqueued too (SegCtl::narrow == 2 picks them)
-	// ... sorts to go before the next attempt, doubled by every attempt that is called off; per kind of sort (4- / 8-byte keys,
-	// rank sorts, keys + payload): what one kind's inputs look like says nothing about another's
-	u32 blind_skip[4] = {0, 0, 0, 0}, blind_backoff[4] = {0, 0, 0, 0};
-	u32 log_skip = 0, log_backoff = 0;       // ... and the same for the attempts by (bit length, mantissa) digits (sort_keys_log): a refused or lost one costs 65 us and more
-	bool blind_no_room = false;              // the slots could not be allocated once: not asked for again (until rsx_reload_env)
-	u32 env_epoch = 0;                       // ... forgotten when rsx_reload_env() has run since
-	SegCtl *host_segctl = nullptr, *dev_host_segctl = nullptr;   // pinned, written by rsx_seg_plan_kernel
-	hipEvent_t seg_ev = nullptr;
-	Plan *host_plan = nullptr;   // pinned, written by the kernels themselves (dev_host_plan: its device address)
-	Plan *dev_host_plan = nullptr;
-	hipEvent_t plan_ev = nullptr;   // recorded behind the plan's copy to the host
-	u64 *host_hist = nullptr;    // pinned, 256 u64
-	// Small sorts of host buffers (rsx_sort, rsx_sort_rank on arrays the one-launch kernels take): pinned, mapped staging the
-	// kernel reads and writes over PCIe itself -- one launch and one synchronisation instead of two copies around them.
-	char *hstage = nullptr, *hstage_dev = nullptr;
-	static constexpr size_t HSTAGE_BYTES = 5 * (size_t)SMALL_SORT_BYTES;   // keys, keys, and two halves of 8-byte indices
-
-	bool fast = false;           // rsx_scatter2_kernel allowed on this device (LDS atomic order verified)
-	// The reference is re-entrant (concurrent calls on disjoint buffers are safe); here calls that share a context
-	// (same device and stream) share its workspace, so every entry point holds this for its duration.
-	std::recursive_mutex mu;
-
-	// The library's own contexts hold TWO sets of flags and histograms and alternate between them (`gen`): small sorts zero
-	// the set of the next sort inside this sort's histogram kernel instead of launching a kernel for it (plan_phase).  A
-	// context in a caller's workspace (external) has one set.
-	u32 gen = 0;
-	static constexpr size_t SMALL_BYTES = 256, HIST_SET_BYTES = 8 * 256 * sizeof(u64);
-	char *small_set() const { return (char *)small.p + (small.external ? 0 : gen * SMALL_BYTES); }
-	char *small_set_other() const { return (char *)small.p + (gen ^ 1u) * SMALL_BYTES; }
-	u64 *ghist() const { return (u64 *)((char *)hist.p + (hist.external ? 0 : gen * HIST_SET_BYTES)); }
-	u64 *ghist_other() const { return (u64 *)((char *)hist.p + (gen ^ 1u) * HIST_SET_BYTES); }
-	u32 *unsorted() const { return (u32 *)small_set(); }
-	u32 *plan_done() const { return (u32 *)(small_set() + 52); }   // blocks of rsx_plan_kernel that are through
-	u64 *verify_bad() const { return (u64 *)(small_set() + 56); }  // RSX_VERIFY: mismatches found by rsx_verify_tile_kernel
-	u32 *hotd() const { return (u32 *)(small_set() + 16); }   // [8] hot digits per column + [1] valid bits (rsx_plan_kernel)
-	Plan *plan() const { return (Plan *)(small_set() + 64); }
-	u32 *kept() const { return (u32 *)(small_set() + 128); }
-	u32 *colmax() const { return (u32 *)(small_set() + 192); }   // [8] largest bin per column (rsx_plan_kernel, kept[16..])
-
-	int init()
-	{
-		RSX_TRY(small.ensure(2 * SMALL_BYTES));
-		RSX_TRY(hist.ensure(2 * HIST_SET_BYTES));
-		RSX_TRY(gscan.ensure(256 * sizeof(u64)));
-		HIP_TRY(hipMemset(small.p, 0, 2 * SMALL_BYTES));   // (both sets start out zeroed: see `gen`)
-		HIP_TRY(hipMemset(hist.p, 0, 2 * HIST_SET_BYTES));
-		if (!host_plan)
-		{
-			HIP_TRY(hipHostMalloc((void **)&host_plan, sizeof(Plan), hipHostMallocMapped));
-			HIP_TRY(hipHostGetDevicePointer((void **)&dev_host_plan, host_plan, 0));
-		}
-		if (!host_hist)
-			HIP_TRY(hipHostMalloc((void **)&host_hist, 256 * sizeof(u64), hipHostMallocDefault));
-		if (!host_segctl) {
-			HIP_TRY(hipHostMalloc((void **)&host_segctl, sizeof(SegCtl), hipHostMallocMapped));
-			HIP_TRY(hipHostGetDevicePointer((void **)&dev_host_segctl, host_segctl, 0));
-		}
-		return RSX_OK;
-	}
-	int ensure_hstage()
-	{
-		if (!hstage) {
-			HIP_TRY(hipHostMalloc((void **)&hstage, HSTAGE_BYTES, hipHostMallocMapped));
-			HIP_TRY(hipHostGetDevicePointer((void **)&hstage_dev, hstage, 0));
-		}
-		return RSX_OK;
-	}
-	void release()
-	{
-		if (hstage)
-			(void)hipHostFree(hstage);
-		hstage = hstage_dev = nullptr;
-		small.release();
-		hist.release();
-		hpart.release();
-		status.release();
-		for (int i = 0; i < 2; ++i) {
-			keys[i].release();
-			vals[i].release();
-			recs[i].release();
-		}
-		tkeys.release();
-		ckeys.release();
-		joint.release();
-		seg.release();
-		slack.release();
-		slack1.release();
-		logb.release();
-		logslots.release();
-		ubits.release();
-		urecs.release();
-		tkctl.release();
-		tkpairs.release();
-		tkcand.release();
-		tkout.release();
-		nthctl.release();
-		nthcand.release();
-		nthio.release();
-		nthout.release();
-		lexkeys.release();
-		lexidx.release();
-		lexstage.release();
-		if (host_logctl)
-			(void)hipHostFree(host_logctl);
-		host_logctl = nullptr;
-		if (log_ev)
-			(void)hipEventDestroy(log_ev);
-		log_ev = nullptr;
-		slack1_v.release();
-		slack_v.release();
-		vasync.release();
-		vsum.release();
-		gscan.release();
-		if (host_segctl)
-			(void)hipHostFree(host_segctl);
-		host_segctl = dev_host_segctl = nullptr;
-		if (seg_ev)
-			(void)hipEventDestroy(seg_ev);
-		seg_ev = nullptr;
-		if (plan_ev)
-			(void)hipEventDestroy(plan_ev);
-		plan_ev = nullptr;
-		if (host_plan)
-			(void)hipHostFree(host_plan);
-		if (host_hist)
-			(void)hipHostFree(host_hist);
-		host_plan = nullptr;
-		host_hist = nullptr;
-	}
-};
-
-std::mutex g_mu;
-std::map<std::pair<int, void *>, Ctx *> g_ctx;
-std::map<int, int> g_lds_order_ok;   // device -> result of lds_order_selfcheck (1 ok, 0 not)
-
-// ---- RSX_HOST_REGISTER=1 (a measurement switch): the caller's host buffers are page-locked (hipHostRegister) FOR THE
-// DURATION OF THE CALL, so that the copies go by DMA straight from / to them instead of through the runtime's bounce buffers.
-// (Round 2 kept registrations cached per pointer across calls: a buffer freed and reallocated at the same address then
-// reused a stale mapping, and evicting an entry could pull the registration from under another thread's copy.  Measured
-// gain of keeping buffers registered: 1-2 %; a caller that wants it registers its own buffers with
-// hipHostRegister -- the library copies from registered memory as it finds it.)
-struct HostRegScope {
-	void *p = nullptr;
-	HostRegScope(void *ptr, size_t bytes)
-	{
-		if (!env().host_register || bytes < ((size_t)1 << 20))
-			return;
-		if (hipHostRegister(ptr, bytes, hipHostRegisterDefault) == hipSuccess)
-			p = ptr;
-		(void)hipGetLastError();   // (a buffer that cannot be registered -- or already is -- is copied as it is)
-	}
-	~HostRegScope()
-	{
-		if (p)
-			(void)hipHostUnregister(p);
-	}
-	HostRegScope(const HostRegScope &) = delete;
-	HostRegScope &operator=(const HostRegScope &) = delete;
-};
-
-// ---- optional HIP-event bracketing of the kernels (rsx_profile_begin/end) ------
-struct ProfRec {
-	int kind;   // 0 histogram, 1 scatter, 2 leaves (rsx_hybrid.hpp), 3 passes that write narrowed keys into slots
-	hipEvent_t start, stop;
-	u64 bytes;
-	hipStream_t stream;
-	bool called_off;   // launches of an attempt the device called off (or of a route the plan did not choose): they returned at
-	                   // once or their output was discarded -- their time is booked apart, their bytes are not booked at all
-	// device-scheduled sorts (rsx_sort_inplace_async): nobody reads a verdict back while the sort is enqueued, so the record names
-	// a pinned word that receives SegCtl::mode behind the attempt (prof_verdict_slot) and which value makes it count:
-	// valid_if 1 -- the attempt's own launches: SEG_MODE_LEAVES; 2 -- the gated histogram-first launches behind it: anything else
-	const u32 *verdict = nullptr;
-	int valid_if = 0;
-};
-bool g_prof_on = false;
-std::vector<ProfRec> g_prof;
-std::mutex g_prof_mu;
-
-// What a sort books is what the DEVICE chose.  Kernels are enqueued before the host knows the route (a sort without a histogram
-// may be called off by its sample; leaves are launched in every shape the plan may ask for); once the host has the verdict it
-// takes the records of the launches that did nothing out of the byte count (prof_called_off) or corrects their bytes
-// (prof_rebook: 8-byte keys whose level-2 slots the sample narrowed to four bytes).  prof_mark() = where this call's records start.
-size_t prof_mark()
-{
-	if (!g_prof_on)
-		return 0;
-	std::lock_guard<std::mutex> lock(g_prof_mu);
-	return g_prof.size();
-}
-void prof_called_off(size_t mark, hipStream_t s, int kind = -1)
-{
-	if (!g_prof_on)
-		return;
-	std::lock_guard<std::mutex> lock(g_prof_mu);
-	for (size_t i = mark; i < g_prof.size(); ++i)
-		if (g_prof[i].stream == s && (kind < 0 || g_prof[i].kind == kind))
-			g_prof[i].called_off = true;
-}
-// (the LAST record of `kind` since the mark: a sort's level-1 and level-2 passes are both kind 1, in that order)
-void prof_rebook(size_t mark, hipStream_t s, int kind, u64 bytes, int new_kind = -1)
-{
-	if (!g_prof_on)
-		return;
-	std::lock_guard<std::mutex> lock(g_prof_mu);
-	for (size_t i = g_prof.size(); i > mark; --i)
-		if (g_prof[i - 1].stream == s && g_prof[i - 1].kind == kind && !g_prof[i - 1].called_off) {
-			g_prof[i - 1].bytes = bytes;
-			if (new_kind >= 0)
-				g_prof[i - 1].kind = new_kind;
-			break;
-		}
-}
-
-// a pinned word for one device-scheduled sort's verdict (4096 per profile window; none left: the records stay as they are)
-u32 *g_prof_vblock = nullptr;
-size_t g_prof_vnext = 0;
-u32 *prof_verdict_slot()
-{
-	std::lock_guard<std::mutex> lock(g_prof_mu);
-	if (!g_prof_vblock && hipHostMalloc((void **)&g_prof_vblock, 4096 * sizeof(u32), hipHostMallocDefault) != hipSuccess) {
-		(void)hipGetLastError();
-		g_prof_vblock = nullptr;
-		return nullptr;
-	}
-	if (g_prof_vnext >= 4096)
-		return nullptr;
-	u32 *p = g_prof_vblock + g_prof_vnext++;
-	*p = 0;
-	return p;
-}
-void prof_tag(size_t from, size_t to, hipStream_t s, const u32 *verdict, int valid_if)
-{
-	std::lock_guard<std::mutex> lock(g_prof_mu);
-	for (size_t i = from; i < to && i < g_prof.size(); ++i)
-		if (g_prof[i].stream == s) {
-			g_prof[i].verdict = verdict;
-			g_prof[i].valid_if = valid_if;
-		}
-}
-// ... around the attempt and the gated launches of a device-scheduled sort (`attempted`: an attempt was enqueued at all)
-struct ProfAsyncVerdict {
-	size_t m0 = 0, m1 = 0;
-	u32 *slot = nullptr;
-	hipStream_t stream;
-	explicit ProfAsyncVerdict(hipStream_t s) : stream(s) { m0 = prof_mark(); }
-	void attempt_enqueued(const SegCtl *ctl)
-	{
-		if (!g_prof_on)
-			return;
-		slot = prof_verdict_slot();
-		if (slot && hipMemcpyAsync(slot, &ctl->mode, sizeof(u32), hipMemcpyDeviceToHost, stream) != hipSuccess) {
-			(void)hipGetLastError();
-			slot = nullptr;
-		}
-		m1 = prof_mark();
-	}
-	void gated_enqueued()
-	{
-		if (!g_prof_on || !slot)
-			return;
-		const size_t m2 = prof_mark();
-		prof_tag(m0, m1, stream, slot, 1);
-		prof_tag(m1, m2, stream, slot, 2);
-	}
-};
-
-struct ProfScope {
-	bool on;
-	ProfRec rec;
-	hipStream_t stream;
-	ProfScope(int kind, u64 bytes, hipStream_t s) : on(g_prof_on), stream(s)
-	{
-		if (!on)
-			return;
-		rec.kind = kind;
-		rec.bytes = bytes;
-		rec.stream = s;
-		rec.called_off = false;
-		if (hipEventCreate(&rec.start) != hipSuccess || hipEventCreate(&rec.stop) != hipSuccess) {
-			on = false;
-			return;
-		}
-		(void)hipEventRecord(rec.start, stream);
-	}
-	~ProfScope()
-	{
-		if (!on)
-			return;
-		(void)hipEventRecord(rec.stop, stream);
-		std::lock_guard<std::mutex> lock(g_prof_mu);
-		g_prof.push_back(rec);
-	}
-};
-int g_devcount = -2;   // -2: not probed
-
-int probe_devices()
-{
-	if (g_devcount != -2)
-		return g_devcount;
-	int n = 0;
-	hipError_t e = hipGetDeviceCount(&n);
-	if (e != hipSuccess) {
-		(void)hipGetLastError();
-		n = 0;
-	}
-	int usable = 0;
-	for (int d = 0; d < n; ++d) {
-		hipDeviceProp_t prop;
-		if (hipGetDeviceProperties(&prop, d) == hipSuccess && strncmp(prop.gcnArchName, "gfx950", 6) == 0)
-			++usable;
-		else
-			(void)hipGetLastError();
-	}
-	g_devcount = usable;
-	return usable;
-}
-
-// rsx_scatter2_kernel ranks keys with returning LDS atomics and needs them to resolve same-address lanes
-// in lane order.  gfx950 does, but that is an observed property, not a documented one: verify it once
-// per device (about a millisecond) and otherwise stay on the table-based ranking of rsx_scatter_kernel.
-int lds_order_selfcheck(int dev)
-{
-	auto it = g_lds_order_ok.find(dev);
-	if (it != g_lds_order_ok.end())
-		return it->second;
-	int ok = 0;
-	u64 *d_bad = nullptr;
-	if (!env().force_table_rank && hipMalloc((void **)&d_bad, sizeof(u64)) == hipSuccess) {
-		u64 bad = ~0ull;
-		if (hipMemset(d_bad, 0, sizeof(u64)) == hipSuccess) {
-			// two shapes: eight waves of bare atomics on collision-heavy digits, and the production shape of
-			// rsx_scatter2_kernel (16 waves, eight atomics in flight, staging stores and 16-byte rows between them)
-			hipLaunchKernelGGL(rsx_lds_order_check_kernel, dim3(1024), dim3(512), 0, 0, d_bad, 0x9E3779B9u, 512);
-			hipLaunchKernelGGL(rsx_lds_order_check2_kernel, dim3(512), dim3(1024), 0, 0, d_bad, 0x85EBCA6Bu, 256);
-			if (hipGetLastError() == hipSuccess && hipDeviceSynchronize() == hipSuccess &&
-			    hipMemcpy(&bad, d_bad, sizeof(u64), hipMemcpyDeviceToHost) == hipSuccess)
-				ok = bad == 0;
-		}
-		(void)hipFree(d_bad);
-	}
-	(void)hipGetLastError();
-	g_lds_order_ok[dev] = ok;
-	return ok;
-}
-
-// ---- rsx_capture_histogram: the caller-supplied Hist of rs_sort_main (radix_sort.hpp:28-33) -------------------------
-// Armed per thread; the next sort of that thread that runs the histogram kernels writes the raw per-column digit counts
-// there (hist[256 j + d]) and disarms.  The counts are recovered from the exclusive offsets the plan kernel leaves in the
-// workspace (every column is scanned, kept or not): count[d] = offset[d + 1] - offset[d], the last one n - offset[255].
-thread_local u64 *g_capture_dst = nullptr;
-thread_local size_t g_capture_entries = 0;
-
-inline bool capture_armed() { return g_capture_dst != nullptr; }
-
-int capture_hist(Ctx &c, size_t n, size_t kb)
-{
-	if (!g_capture_dst)
-		return RSX_OK;
-	u64 *dst = g_capture_dst;
-	const size_t entries = g_capture_entries;
-	g_capture_dst = nullptr;
-	g_capture_entries = 0;
-	if (entries < 256 * kb)
-		return fail(RSX_EINVAL, "rsx_capture_histogram: room for %zu entries, the sort has %zu", entries, 256 * kb);
-	std::vector<u64> off(256 * kb);
-	HIP_TRY(hipMemcpyAsync(off.data(), c.ghist(), 256 * kb * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	for (size_t j = 0; j < kb; ++j)
-		for (size_t d = 0; d < 256; ++d)
-			dst[256 * j + d] = (d == 255 ? (u64)n : off[256 * j + d + 1]) - off[256 * j + d];
-	return RSX_OK;
-}
-
-// RSX_VERIFY=1 (read once per process): after every host-scheduled scatter pass of the fast kernel one pseudo-randomly
-// chosen tile is re-ranked without LDS atomics (rsx_verify_tile_kernel) and compared with what the pass wrote; a
-// mismatch fails the call with RSX_EVERIFY.  Passes are then serialised by the check's read-back and no pass is
-// speculative; the *_inplace_async entry points, which never synchronise, are not verified.
-bool verify_mode() { return env().verify; }
-u32 g_verify_seq = 0;
-
-int get_ctx(void *stream, Ctx **out)
-{
-	std::lock_guard<std::mutex> lock(g_mu);
-	if (probe_devices() <= 0)
-		return fail(RSX_ENODEVICE, "no gfx950 (MI355X) device visible to HIP; this library has no CPU path");
-	int dev = 0;
-	HIP_TRY(hipGetDevice(&dev));
-	auto key = std::make_pair(dev, stream);
-	auto it = g_ctx.find(key);
-	if (it == g_ctx.end()) {
-		Ctx *c = new Ctx();
-		c->device = dev;
-		c->stream = (hipStream_t)stream;
-		c->fast = lds_order_selfcheck(dev) != 0;
-		int rc = c->init();
-		if (rc != RSX_OK) {
-			c->release();
-			delete c;
-			return rc;
-		}
-		it = g_ctx.emplace(key, c).first;
-	}
-	*out = it->second;
-	return RSX_OK;
-}
-
-void info_clear(rsx_info *info, int dtype)
-{
-	if (!info)
-		return;
-	memset(info, 0, sizeof(*info));
-	info->key_bytes = (uint32_t)dtype_size(dtype);
-}
-
-void info_from_plan(rsx_info *info, const Plan &p)
-{
-	if (!info)
-		return;
-	info->ncols = p.ncols;
-	for (u32 i = 0; i < p.ncols && i < 8; ++i)
-		info->cols[i] = p.cols[i];
-}
 
 // tiles per super-tile: as many as keeps at least ~2048 super-tiles in flight, at most 8
 u32 choose_tps(size_t n, size_t tile)
@@ -3676,683 +2871,11 @@ int msd_split_known(Ctx &c, const KT *src, KT *dst, size_t n, int dtype, int ord
 	                               hot ? hot_flags(1u << col, col) : 0u);
 }
 
-// ---- rsx_sort_unique_device: the distinct keys in order, by bitmap or count table where they fit (rsx_unique.hpp) ------
-// The sizes at which the ordinary sort would go without a histogram (blind_wanted's, without spending its back-off): there
-// a sample of the keys is looked at first, so that evenly spread keys never pay a histogram the sort would not have paid.
-template <typename KT> bool unique_sample_wanted(const Ctx &c, size_t n)
-{
-	if constexpr (sizeof(KT) < 4)
-		return false;
-	if (env().no_blind || env().no_slack || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() || c.small.external ||
-	    env().no_speculation)
-		return false;
-	if (n < ((size_t)1 << 22) || n >= blind_keys_end<KT>())
-		return false;
-	size_t floor_keys = sizeof(KT) == 8 ? (size_t)9 << 19 : (size_t)15 << 19;
-	if (env().blind_min_log2)
-		floor_keys = (size_t)1 << env().blind_min_log2;
-	floor_keys = std::min(floor_keys, (size_t)1 << env().two_level_min_log2);
-	return n >= floor_keys;
-}
-
-inline u64 *unique_hdr(Ctx &c) { return (u64 *)c.urecs.p; }
-inline UniqueRec *unique_recs(Ctx &c) { return (UniqueRec *)((u64 *)c.urecs.p + 8); }
-
-// the number of distinct keys a read-out left in the header, once the stream is through
-inline int unique_total(Ctx &c, size_t *n_unique)
-{
-	u64 total = 0;
-	HIP_TRY(hipMemcpyAsync(&total, unique_hdr(c), sizeof total, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	*n_unique = (size_t)total;
-	return RSX_OK;
-}
-
-// the sorted array `in` compacted into `out`: count the heads per tile, scan, write (12 bytes per 4-byte key)
-template <typename KT>
-int unique_compact(Ctx &c, const KT *in, KT *out, size_t n, void *counts, size_t count_bytes, size_t *n_unique)
-{
-	const u64 tiles = ((u64)n + unique_heads_tile<KT>() - 1) / unique_heads_tile<KT>();
-	RSX_TRY(c.urecs.ensure(64 + (size_t)tiles * sizeof(UniqueRec)));
-	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 0>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c),
-	                   (KT *)nullptr, (void *)nullptr, 0u);
-	hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), tiles, unique_hdr(c));
-	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 1>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c), out,
-	                   counts, (u32)count_bytes);
-	HIP_TRY(hipGetLastError());
-	return unique_total(c, n_unique);
-}
-
-// routes 1 and 2: every key sets its bit, the bitmap is read out in order.  *done = 0: no room for the bitmap.
-template <typename KT>
-int unique_bitmap(Ctx &c, const KT *src, KT *out, size_t n, KdfArgs<KT> ka, u64 vary, u32 vbits, const BitRuns &runs, size_t *n_unique,
-                  rsx_unique_info *info, int *done)
-{
-	*done = 0;
-	if constexpr (sizeof(KT) >= 2) {
-		const u64 words = std::max<u64>(UNIQUE_CHUNK_WORDS, ((u64)1 << vbits) / 32);   // (a multiple of the read-out's chunk)
-		const u64 chunks = words / UNIQUE_CHUNK_WORDS;
-		if (c.ubits.ensure((size_t)words * sizeof(u32)) != RSX_OK || c.urecs.ensure(64 + (size_t)chunks * sizeof(UniqueRec)) != RSX_OK)
-			return RSX_OK;   // (not an error: the caller takes the sort)
-		u32 *bitmap = (u32 *)c.ubits.p;
-		HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)words * sizeof(u32), c.stream));
-		// Two workgroups of 1024 threads fill a CU (2048 threads; 2 x 8 or 2 x 32 KiB of its 160 KiB of LDS); the 128 KiB form
-		// leaves room for one.  A workgroup should have at least four sweeps of its own to pay for zeroing and merging its bitmap.
-		const u64 nvec = (u64)n * sizeof(KT) / 16;
-		const u32 full = vbits > 18 && vbits <= 20 ? 256u : 512u;
-		const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>(full, nvec / 16384));
-		if (vbits <= 16)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 16>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else if (vbits <= 18)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 18>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else if (vbits <= 20)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 20>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 0>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		hipLaunchKernelGGL((rsx_unique_expand_kernel<KT, 0>), dim3((unsigned)chunks), dim3(256), 0, c.stream, (const u32 *)bitmap,
-		                   unique_recs(c), (KT *)nullptr, src, ka, runs, (KT)vary);
-		hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), chunks, unique_hdr(c));
-		hipLaunchKernelGGL((rsx_unique_expand_kernel<KT, 1>), dim3((unsigned)chunks), dim3(256), 0, c.stream, (const u32 *)bitmap,
-		                   unique_recs(c), out, src, ka, runs, (KT)vary);
-		HIP_TRY(hipGetLastError());
-		info->route = vbits <= 20 ? RSX_UNIQUE_BITMAP_LDS : RSX_UNIQUE_BITMAP_GLOBAL;
-		info->table_bytes = (u64)words * sizeof(u32);
-		*done = 1;
-		return unique_total(c, n_unique);
-	}
-	return RSX_OK;
-}
-
-template <typename KT>
-int sort_unique_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order, void *counts, size_t count_bytes, void **result,
-                       size_t *n_unique, rsx_unique_info *info)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	const u32 max_bits = env().unique_max_bits;
-	RSX_TRY(c.urecs.ensure(64 + 64 * sizeof(UniqueRec)));
-	bool have_plan = false, to_sort = false;
-	Plan plan{};
-	if (unique_sample_wanted<KT>(c, n)) {
-		// The sample can only PROVE that many bits vary (a bit that differs between two sampled keys differs among the keys):
-		// more than any bitmap or table here takes, and the keys go to the sort as if this entry point were rsx_sort_device.
-		const u64 init[2] = {0, ~0ull};
-		u64 got[2];
-		HIP_TRY(hipMemcpyAsync(unique_hdr(c), init, sizeof init, hipMemcpyHostToDevice, c.stream));
-		hipLaunchKernelGGL((rsx_unique_sample_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, ka, unique_hdr(c));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(got, unique_hdr(c), sizeof got, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const u32 limit = !max_bits ? 0u : counts ? 8u : max_bits;   // (with counts: one kept column at most)
-		to_sort = (u32)__builtin_popcountll(got[0] ^ got[1]) > limit;
-	}
-	u64 vary = 0;
-	u32 vbits = 0;
-	if (!to_sort) {
-		RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, 0));
-		have_plan = true;
-		info_from_plan(&info->sort, plan);
-		vary = ((u64)plan.vary_hi << 32) | plan.vary_lo;
-		vbits = (u32)__builtin_popcountll(vary);
-		info->varying_bits = vbits;
-		if (plan.sorted)
-			info->sort.early_exit = 2;
-		if (vary == 0) {
-			// every key equal: the first one, n times
-			info->route = RSX_UNIQUE_TRIVIAL;
-			*result = src;
-			*n_unique = 1;
-			if (counts) {
-				const u64 c64 = n;
-				const u32 c32 = (u32)n;
-				HIP_TRY(hipMemcpyAsync(counts, count_bytes == 4 ? (const void *)&c32 : (const void *)&c64, count_bytes, hipMemcpyHostToDevice,
-				                       c.stream));
-				HIP_TRY(hipStreamSynchronize(c.stream));
-			}
-			return RSX_OK;
-		}
-		if (max_bits && plan.ncols == 1) {
-			// one kept column: its 256 counts are the answer (the scanned histogram the plan left), no key is read again
-			const u32 col = plan.cols[0];
-			hipLaunchKernelGGL((rsx_unique_table_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const u64 *)(c.ghist() + 256 * col),
-			                   (const u32 *)nullptr, 256u, (u64)n, 8 * col, (const KT *)src, ka, aux, counts, (u32)count_bytes, unique_hdr(c));
-			HIP_TRY(hipGetLastError());
-			info->route = RSX_UNIQUE_TABLE;
-			info->table_bytes = 256 * sizeof(u64);
-			*result = aux;
-			info->sort.result_in_aux = 1;
-			return unique_total(c, n_unique);
-		}
-		if constexpr (sizeof(KT) == 2) {
-			// 2-byte keys with counts: the joint table of both bytes (32-bit counters: below 2^32 keys; the kernel leaves sorted
-			// input alone, which the compaction below takes without a sort)
-			if (max_bits && counts && plan.ncols == 2 && !plan.sorted && n < ((size_t)1 << 32) &&
-			    c.joint.ensure(65536 * sizeof(u32) + 65537 * sizeof(u64) + 8) == RSX_OK) {
-				u32 *jt = (u32 *)c.joint.p;
-				HIP_TRY(hipMemsetAsync(jt, 0, 65536 * sizeof(u32), c.stream));
-				hipLaunchKernelGGL(rsx_joint16_kernel, dim3(512), dim3(1024), 0, c.stream, (const uint16_t *)src, (u64)n, ka, jt,
-				                   (const Plan *)c.plan());
-				hipLaunchKernelGGL((rsx_unique_table_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const u64 *)nullptr, (const u32 *)jt,
-				                   65536u, (u64)n, 0u, (const KT *)src, ka, aux, counts, (u32)count_bytes, unique_hdr(c));
-				HIP_TRY(hipGetLastError());
-				info->route = RSX_UNIQUE_TABLE;
-				info->table_bytes = 65536 * sizeof(u32);
-				*result = aux;
-				info->sort.result_in_aux = 1;
-				return unique_total(c, n_unique);
-			}
-		}
-		BitRuns runs;
-		if (!counts && vbits <= max_bits && bit_runs(vary, &runs)) {
-			int done = 0;
-			RSX_TRY(unique_bitmap<KT>(c, src, aux, n, ka, vary, vbits, runs, n_unique, info, &done));
-			if (done) {
-				*result = aux;
-				info->sort.result_in_aux = 1;
-				return RSX_OK;
-			}
-		}
-	}
-	// the ordinary sort (any route; every early exit), then one compaction of the sorted buffer into the other one
-	info->route = RSX_UNIQUE_SORT;
-	KT *in = src;
-	if (!(have_plan && plan.sorted)) {
-		void *res = nullptr;
-		rsx_info si;
-		info_clear(&si, dtype);
-		RSX_TRY(sort_keys_device<KT>(c, src, aux, n, dtype, order, &res, &si));
-		info->sort = si;
-		in = (KT *)res;
-	}
-	KT *out = in == src ? aux : src;
-	RSX_TRY(unique_compact<KT>(c, in, out, n, counts, count_bytes, n_unique));
-	*result = out;
-	info->sort.result_in_aux = out == aux;
-	return RSX_OK;
-}
-
-// ---- rsx_sort_topk_device: the first k of the stable sorted order by MSD radix select (rsx_topk.hpp) --------------------
-// Default route: select from TOPK_MIN_N keys on while k <= n / TOPK_MAX_K_DIV; the ordinary rank sort otherwise.
-// The candidate buffer takes a selected bucket of at most n / 8 + 1024 elements (topk_cap); a larger one is narrowed by
-// further histograms over the input.
-constexpr size_t TOPK_MIN_N = (size_t)1 << 18, TOPK_MAX_K_DIV = 8;
-inline size_t topk_cap(size_t n) { return n / 8 + 1024; }
-
-struct TopkLayout {
-	u64 groups, chunk;     // the input: workgroups and elements of each one's range
-	u64 cgroups, cchunk;   // the candidate buffer at its capacity
-	size_t rows, crows, goff, cgoff, bytes;
-};
-
-template <typename KT> TopkLayout topk_layout(size_t n)
-{
-	const u64 tile = topk_tile<KT>();
-	auto split = [&](u64 m, u64 *groups, u64 *chunk) {
-		const u64 tiles = std::max<u64>(1, (m + tile - 1) / tile);
-		*groups = std::min<u64>(TOPK_MAX_GROUPS, tiles);
-		*chunk = (tiles + *groups - 1) / *groups * tile;
-	};
-	TopkLayout L;
-	split(n, &L.groups, &L.chunk);
-	split(topk_cap(n), &L.cgroups, &L.cchunk);
-	L.rows = sizeof(TopkCtl);
-	L.crows = L.rows + (size_t)L.groups * TOPK_ROW * sizeof(u32);
-	L.goff = L.crows + (size_t)L.cgroups * TOPK_ROW * sizeof(u32);
-	L.cgoff = L.goff + (size_t)L.groups * 2 * sizeof(u64);
-	L.bytes = L.cgoff + (size_t)L.cgroups * 2 * sizeof(u64);
-	return L;
-}
-
-inline void topk_info_from_ctl(rsx_topk_info *info, const TopkCtl &h)
-{
-	info->input_reads = h.input_reads;
-	info->digit_passes = h.digit_passes;
-	info->n_less = h.n_less;
-	info->n_equal = h.bucket;
-	info->kth_key = h.kth_raw;
-}
-
-// *done = 0: no room for the buffers (not an error: the caller takes the sort route)
-template <typename KT, typename IT>
-int topk_select(Ctx &c, const KT *src, size_t n, size_t k, int dtype, int order, KT *out_keys, IT *out_idx, rsx_topk_info *info, int *done)
-{
-	*done = 0;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	const TopkLayout L = topk_layout<KT>(n);
-	const size_t cap = topk_cap(n);
-	const size_t kpad = (k + 15) & ~(size_t)15, cpad = (cap + 15) & ~(size_t)15;   // (every array a multiple of 16 bytes)
-	if (c.tkctl.ensure(L.bytes) != RSX_OK || c.tkpairs.ensure(2 * kpad * (sizeof(KT) + sizeof(IT))) != RSX_OK ||
-	    c.tkcand.ensure(cpad * (sizeof(KT) + sizeof(IT))) != RSX_OK)
-		return RSX_OK;
-	char *base = (char *)c.tkctl.p;
-	TopkCtl *ctl = (TopkCtl *)base;
-	u32 *rows = (u32 *)(base + L.rows), *crows = (u32 *)(base + L.crows);
-	u64 *goff = (u64 *)(base + L.goff), *cgoff = (u64 *)(base + L.cgoff);
-	KT *pk = (KT *)c.tkpairs.p, *pk2 = pk + kpad;
-	IT *pi = (IT *)(pk2 + kpad), *pi2 = pi + kpad;
-	KT *ck = (KT *)c.tkcand.p;
-	IT *ci = (IT *)(ck + cpad);
-	(void)ck, (void)ci, (void)crows, (void)cgoff;   // (1-byte keys never fill candidates)
-	TopkCtl h;
-	memset(&h, 0, sizeof h);
-	h.k_rem = k;
-	HIP_TRY(hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, c.stream));
-	const dim3 grid((unsigned)L.groups), cgrid((unsigned)L.cgroups), threads(TOPK_THREADS);
-	const dim3 rgrid((unsigned)((L.groups + 15) / 16)), crgrid((unsigned)((L.cgroups + 15) / 16));
-	const u32 top = 8 * ((u32)sizeof(KT) - 1);
-	// the top digit of every key; a bucket that fits the candidate buffer is moved there by one more pass over the input
-	hipLaunchKernelGGL((rsx_topk_hist_kernel<KT, 0>), grid, threads, 0, c.stream, src, (u64)n, ka, ctl, rows, L.chunk, top);
-	hipLaunchKernelGGL((rsx_topk_pick_kernel<KT>), dim3(1), dim3(256), 0, c.stream, ctl, top, (u64)cap, sizeof(KT) > 1 ? 1u : 0u, ka);
-	if constexpr (sizeof(KT) > 1) {
-		hipLaunchKernelGGL(rsx_topk_rows_kernel, rgrid, dim3(1024), 0, c.stream, (const TopkCtl *)ctl, (const u32 *)rows, (u32)L.groups, top,
-		                   1u, goff);
-		hipLaunchKernelGGL((rsx_topk_write_kernel<KT, IT, 0, 0>), grid, threads, 0, c.stream, src, (const IT *)nullptr, (u64)n, ka, ctl,
-		                   (const u64 *)goff, L.chunk, pk, pi, (u64)k, ck, ci, (u64)cap);
-		// the other digits: in the candidates (mode 1), or in the input under the prefix (mode 0) -- each kernel knows which
-		for (u32 shift = top - 8;; shift -= 8) {
-			hipLaunchKernelGGL((rsx_topk_hist_kernel<KT, 0>), grid, threads, 0, c.stream, src, (u64)n, ka, ctl, rows, L.chunk, shift);
-			hipLaunchKernelGGL((rsx_topk_hist_kernel<KT, 1>), cgrid, threads, 0, c.stream, (const KT *)ck, (u64)0, ka, ctl, crows, L.cchunk,
-			                   shift);
-			hipLaunchKernelGGL((rsx_topk_pick_kernel<KT>), dim3(1), dim3(256), 0, c.stream, ctl, shift, (u64)cap, 0u, ka);
-			if (!shift)
-				break;
-		}
-	}
-	// the final filter: exactly k pairs -- everything below the k-th key, then the first k - n_less elements equal to it
-	hipLaunchKernelGGL(rsx_topk_rows_kernel, rgrid, dim3(1024), 0, c.stream, (const TopkCtl *)ctl, (const u32 *)rows, (u32)L.groups, 0u, 0u,
-	                   goff);
-	hipLaunchKernelGGL((rsx_topk_write_kernel<KT, IT, 0, 1>), grid, threads, 0, c.stream, src, (const IT *)nullptr, (u64)n, ka, ctl,
-	                   (const u64 *)goff, L.chunk, pk, pi, (u64)k, (KT *)nullptr, (IT *)nullptr, (u64)0);
-	if constexpr (sizeof(KT) > 1) {
-		hipLaunchKernelGGL(rsx_topk_rows_kernel, crgrid, dim3(1024), 0, c.stream, (const TopkCtl *)ctl, (const u32 *)crows, (u32)L.cgroups,
-		                   0u, 1u, cgoff);
-		hipLaunchKernelGGL((rsx_topk_write_kernel<KT, IT, 1, 1>), cgrid, threads, 0, c.stream, (const KT *)ck, (const IT *)ci, (u64)0, ka, ctl,
-		                   (const u64 *)cgoff, L.cchunk, pk, pi, (u64)k, (KT *)nullptr, (IT *)nullptr, (u64)0);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(&h, ctl, offsetof(TopkCtl, table), hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	topk_info_from_ctl(info, h);
-	// the k pairs sorted by the library's stable sorts (their scratch is the context's other buffers), and copied out
-	KT *rk = pk;
-	IT *ri = pi;
-	if (k > 1) {
-		rsx_info si;
-		info_clear(&si, dtype);
-		if (out_idx) {
-			RSX_TRY((sort_pairs_device<KT, IT>(c, pk, pk2, pi, pi2, k, dtype, order, &si)));
-			if (si.result_in_aux) {
-				rk = pk2;
-				ri = pi2;
-			}
-		} else {
-			void *res = nullptr;
-			RSX_TRY(sort_keys_device<KT>(c, pk, pk2, k, dtype, order, &res, &si));
-			rk = (KT *)res;
-		}
-	}
-	if (out_keys)
-		HIP_TRY(hipMemcpyAsync(out_keys, rk, k * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
-	if (out_idx)
-		HIP_TRY(hipMemcpyAsync(out_idx, ri, k * sizeof(IT), hipMemcpyDeviceToDevice, c.stream));
-	info->route = RSX_TOPK_SELECT;
-	*done = 1;
-	return RSX_OK;
-}
-
-// the sort route: rsx_sort_rank_device's machinery on a workspace copy, the first k ranks and the keys gathered through them
-template <typename KT, typename IT>
-int topk_by_sort(Ctx &c, const KT *src, size_t n, size_t k, int dtype, int order, KT *out_keys, IT *out_idx, rsx_topk_info *info)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	RSX_TRY(c.vals[0].ensure(2 * n * sizeof(IT)));
-	RSX_TRY(c.tkctl.ensure(sizeof(TopkCtl)));
-	TopkCtl *ctl = (TopkCtl *)c.tkctl.p;
-	void *res = nullptr;
-	rsx_info ri;
-	info_clear(&ri, dtype);
-	RSX_TRY((sort_rank_device<KT, IT>(c, src, (IT *)c.vals[0].p, n, dtype, order, &res, &ri)));
-	HIP_TRY(hipMemsetAsync(ctl, 0, offsetof(TopkCtl, table), c.stream));
-	hipLaunchKernelGGL((rsx_topk_gather_kernel<KT, IT>), dim3((unsigned)std::min<u64>(1024, ((u64)k + 255) / 256)), dim3(256), 0, c.stream, src,
-	                   (const IT *)res, (u64)k, out_keys, out_idx, ka, ctl);
-	const u64 sweep = (u64)TOPK_THREADS * (16 / sizeof(KT));
-	hipLaunchKernelGGL((rsx_topk_count_kernel<KT>), dim3((unsigned)std::min<u64>(1024, ((u64)n + sweep - 1) / sweep)), dim3(TOPK_THREADS), 0,
-	                   c.stream, src, (u64)n, ka, ctl);
-	HIP_TRY(hipGetLastError());
-	TopkCtl h;
-	HIP_TRY(hipMemcpyAsync(&h, ctl, offsetof(TopkCtl, table), hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	topk_info_from_ctl(info, h);
-	info->route = RSX_TOPK_SORT;
-	return RSX_OK;
-}
-
-template <typename KT, typename IT>
-int sort_topk_device(Ctx &c, const KT *src, size_t n, size_t k, int dtype, int order, KT *out_keys, IT *out_idx, rsx_topk_info *info)
-{
-	const unsigned force = env().topk_force;
-	if (force == 1 || (force == 0 && n >= TOPK_MIN_N && k <= n / TOPK_MAX_K_DIV)) {
-		int done = 0;
-		RSX_TRY((topk_select<KT, IT>(c, src, n, k, dtype, order, out_keys, out_idx, info, &done)));
-		if (done)
-			return RSX_OK;
-	}
-	return topk_by_sort<KT, IT>(c, src, n, k, dtype, order, out_keys, out_idx, info);
-}
-
-// ---- rsx_sort_nth_device: the elements at given ranks of the stable sorted order by multi-rank MSD radix select (rsx_nth.hpp) ----
-// Default route: select from NTH_MIN_N keys on while there are at most RSX_NTH_MAX_SELECT_RANKS distinct ranks; the
-// ordinary rank sort otherwise.  The candidate buffer takes active buckets of together at most n / 8 + 1024 elements (nth_cap);
-// larger ones are narrowed by further histograms over the input.
-constexpr size_t NTH_MIN_N = (size_t)1 << 18;
-inline size_t nth_cap(size_t n) { return n / 8 + 1024; }
-static_assert((unsigned)NTH_MAX_RANKS == (unsigned)RSX_NTH_MAX_SELECT_RANKS, "rsx.h and rsx_nth.hpp disagree");
-
-// what the call asks for, prepared by the entry point: the distinct ranks ascending, and the record of each caller position
-struct NthAsk {
-	const uint64_t *ranks;
-	size_t m;
-	std::vector<u64> distinct;
-	std::vector<u32> map;
-	uint64_t *n_less, *n_equal;
-};
-
-struct NthIo {
-	u64 *ranks, *nless, *nequal;
-	u32 *map;
-};
-inline int nth_io(Ctx &c, size_t m, NthIo *io)
-{
-	RSX_TRY(c.nthio.ensure(m * (3 * sizeof(u64) + sizeof(u32))));
-	io->ranks = (u64 *)c.nthio.p;
-	io->nless = io->ranks + m;
-	io->nequal = io->nless + m;
-	io->map = (u32 *)(io->nequal + m);
-	return RSX_OK;
-}
-
-// (behind the kernel that wrote them) the two host arrays; the call returns with them complete, and with the caller's rank
-// list no longer in use
-inline int nth_results_back(Ctx &c, const NthAsk &ask, const NthIo &io)
-{
-	if (ask.n_less)
-		HIP_TRY(hipMemcpyAsync(ask.n_less, io.nless, ask.m * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
-	if (ask.n_equal)
-		HIP_TRY(hipMemcpyAsync(ask.n_equal, io.nequal, ask.m * sizeof(u64), hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	return RSX_OK;
-}
-
-// *done = 0: no room for the buffers, or a wanted key occurs too often for the candidate buffer and indices are wanted (neither
-// is an error: the caller takes the sort route)
-template <typename KT, typename IT>
-int nth_select(Ctx &c, const KT *src, size_t n, const NthAsk &ask, int dtype, int order, KT *out_keys, IT *out_idx, rsx_nth_info *info,
-               int *done)
-{
-	*done = 0;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	const u64 tile = nth_tile<KT>();
-	const u64 tiles = std::max<u64>(1, ((u64)n + tile - 1) / tile);
-	const u64 groups = std::min<u64>(NTH_MAX_GROUPS, tiles);
-	const u64 chunk = (tiles + groups - 1) / groups * tile;
-	const size_t cap = nth_cap(n), cpad = (cap + 15) & ~(size_t)15;   // (every array a multiple of 16 bytes)
-	const size_t table_bytes = (size_t)NTH_MAX_RANKS * 256 * sizeof(u64);
-	const size_t m = ask.m, nd = ask.distinct.size();
-	NthIo io;
-	if (c.nthctl.ensure(sizeof(NthCtl) + table_bytes + (size_t)groups * sizeof(u64)) != RSX_OK ||
-	    c.nthcand.ensure(2 * cpad * (sizeof(KT) + (out_idx ? sizeof(IT) : 0))) != RSX_OK || nth_io(c, m, &io) != RSX_OK)
-		return RSX_OK;
-	char *base = (char *)c.nthctl.p;
-	NthCtl *ctl = (NthCtl *)base;
-	u64 *table = (u64 *)(base + sizeof(NthCtl));
-	u64 *goff = table + (size_t)NTH_MAX_RANKS * 256;
-	KT *ck = (KT *)c.nthcand.p, *ck2 = ck + cpad;
-	IT *ci = out_idx ? (IT *)(ck2 + cpad) : nullptr, *ci2 = out_idx ? ci + cpad : nullptr;
-	NthCtl h;
-	memset(&h, 0, sizeof h);
-	h.nrec = (u32)nd;
-	h.nact = 1;
-	h.act_size[0] = n;
-	for (size_t r = 0; r < nd; ++r)
-		h.rec[r].k_rem = ask.distinct[r];
-	HIP_TRY(hipMemcpyAsync(ctl, &h, sizeof h, hipMemcpyHostToDevice, c.stream));
-	HIP_TRY(hipMemsetAsync(table, 0, table_bytes, c.stream));
-	HIP_TRY(hipMemcpyAsync(io.map, ask.map.data(), m * sizeof(u32), hipMemcpyHostToDevice, c.stream));
-	const dim3 grid((unsigned)groups), threads(NTH_THREADS);
-	const u32 top = 8 * ((u32)sizeof(KT) - 1), want_idx = out_idx ? 1u : 0u;
-	// every level's histogram and pick (those behind the switch to the candidates do nothing), then the candidates' two passes
-	hipLaunchKernelGGL((rsx_nth_hist_kernel<KT, 1>), grid, threads, 0, c.stream, src, (u64)n, ka, (const NthCtl *)ctl, table, chunk, top);
-	hipLaunchKernelGGL((rsx_nth_pick_kernel<KT>), dim3(1), dim3(256), 0, c.stream, ctl, table, top, (u64)cap, want_idx);
-	if constexpr (sizeof(KT) > 1) {
-		for (u32 shift = top - 8;; shift -= 8) {
-			hipLaunchKernelGGL((rsx_nth_hist_kernel<KT, 0>), grid, threads, 0, c.stream, src, (u64)n, ka, (const NthCtl *)ctl, table, chunk,
-			                   shift);
-			hipLaunchKernelGGL((rsx_nth_pick_kernel<KT>), dim3(1), dim3(256), 0, c.stream, ctl, table, shift, (u64)cap, want_idx);
-			if (!shift)
-				break;
-		}
-	}
-	hipLaunchKernelGGL((rsx_nth_count_kernel<KT>), grid, threads, 0, c.stream, src, (u64)n, ka, ctl, goff, chunk);
-	hipLaunchKernelGGL((rsx_nth_write_kernel<KT, IT>), grid, threads, 0, c.stream, src, (u64)n, ka, ctl, (const u64 *)goff, chunk, ck, ci,
-	                   (u64)cap);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipMemcpyAsync(&h, ctl, offsetof(NthCtl, act_prefix), hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	if (h.mode == 0 || (h.mode == 1 && (h.cand_n == 0 || h.cand_n > cap)) || (h.mode == 2 && out_idx))
-		return RSX_OK;
-	// the candidates sorted by the library's stable sorts (their scratch is the context's other buffers)
-	const KT *sk = ck;
-	const IT *si = ci;
-	if (h.mode == 1 && h.cand_n > 1) {
-		rsx_info si_info;
-		info_clear(&si_info, dtype);
-		if (out_idx) {
-			RSX_TRY((sort_pairs_device<KT, IT>(c, ck, ck2, ci, ci2, (size_t)h.cand_n, dtype, order, &si_info)));
-			if (si_info.result_in_aux) {
-				sk = ck2;
-				si = ci2;
-			}
-		} else {
-			void *res = nullptr;
-			RSX_TRY(sort_keys_device<KT>(c, ck, ck2, (size_t)h.cand_n, dtype, order, &res, &si_info));
-			sk = (const KT *)res;
-		}
-	}
-	hipLaunchKernelGGL((rsx_nth_gather_kernel<KT, IT>), dim3((unsigned)std::min<u64>(1024, ((u64)m + 255) / 256)), dim3(256), 0, c.stream,
-	                   (const NthCtl *)ctl, sk, si, (const u32 *)io.map, (u64)m, out_keys, out_idx, io.nless, io.nequal, ka);
-	HIP_TRY(hipGetLastError());
-	RSX_TRY(nth_results_back(c, ask, io));
-	info->route = RSX_NTH_SELECT;
-	info->input_reads = h.input_reads;
-	info->digit_passes = h.digit_passes;
-	info->active_buckets = h.nact;
-	info->from_prefix = h.mode == 2 ? 1 : 0;
-	info->candidates = h.mode == 1 ? h.cand_n : 0;
-	*done = 1;
-	return RSX_OK;
-}
-
-// the sort route: rsx_sort_rank_device's machinery on a workspace copy, the m entries read through the ranks
-template <typename KT, typename IT>
-int nth_by_sort(Ctx &c, const KT *src, size_t n, const NthAsk &ask, int dtype, int order, KT *out_keys, IT *out_idx, rsx_nth_info *info)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	const size_t m = ask.m;
-	NthIo io;
-	RSX_TRY(c.vals[0].ensure(2 * n * sizeof(IT)));
-	RSX_TRY(nth_io(c, m, &io));
-	void *res = nullptr;
-	rsx_info ri;
-	info_clear(&ri, dtype);
-	RSX_TRY((sort_rank_device<KT, IT>(c, src, (IT *)c.vals[0].p, n, dtype, order, &res, &ri)));
-	HIP_TRY(hipMemcpyAsync(io.ranks, ask.ranks, m * sizeof(u64), hipMemcpyHostToDevice, c.stream));
-	hipLaunchKernelGGL((rsx_nth_sorted_kernel<KT, IT>), dim3((unsigned)std::min<u64>(1024, ((u64)m + 255) / 256)), dim3(256), 0, c.stream, src,
-	                   (const IT *)res, (u64)n, (const u64 *)io.ranks, (u64)m, out_keys, out_idx, io.nless, io.nequal, ka);
-	HIP_TRY(hipGetLastError());
-	RSX_TRY(nth_results_back(c, ask, io));
-	info->route = RSX_NTH_SORT;
-	return RSX_OK;
-}
-
-template <typename KT, typename IT>
-int sort_nth_device(Ctx &c, const KT *src, size_t n, const NthAsk &ask, int dtype, int order, KT *out_keys, IT *out_idx, rsx_nth_info *info)
-{
-	const unsigned force = env().nth_force;
-	const size_t nd = ask.distinct.size();
-	if (nd >= 1 && nd <= NTH_MAX_RANKS && (force == 1 || (force == 0 && n >= NTH_MIN_N))) {
-		int done = 0;
-		RSX_TRY((nth_select<KT, IT>(c, src, n, ask, dtype, order, out_keys, out_idx, info, &done)));
-		if (done)
-			return RSX_OK;
-	}
-	return nth_by_sort<KT, IT>(c, src, n, ask, dtype, order, out_keys, out_idx, info);
-}
-
 #include "rsx_multi_state.hpp"   // rsx_sort_multi: per-rank streams, buffers, phases, peer access
 
-#define RSX_DISPATCH_KT(dtype, CALL)                               \
-	switch (dtype_size(dtype)) {                                   \
-	case 1: { typedef uint8_t KT; CALL; } break;                   \
-	case 2: { typedef uint16_t KT; CALL; } break;                  \
-	case 4: { typedef uint32_t KT; CALL; } break;                  \
-	case 8: { typedef u64 KT; CALL; } break;                       \
-	default: return fail(RSX_EINVAL, "unknown dtype %d", (int)(dtype)); \
-	}
-
-// ---- rsx_sort_lex_device: stable argsort by several key columns (rsx_lex.hpp) ------------------------------------------
-// The reference's stability argument one level up: sort by the least significant column first, then stably by the next.
-// GROUPING (deterministic; tests assert it): walk from the last column towards column 0 and put a column into the current
-// group while the group's bytes plus the column's are at most P = Env::lex_pack_bytes; a column wider than P is a group of
-// its own.  group[0] holds the LAST columns and is sorted first.
-void lex_plan(const rsx_lex_col *cols, size_t ncols, u32 P, rsx_lex_info *info)
-{
-	u32 ng = 0, bytes = 0;
-	size_t end = ncols;   // one past the last column of the group being filled
-	auto emit = [&](size_t first) {
-		rsx_lex_group &g = info->group[ng++];
-		g.first_col = (u32)first;
-		g.ncols = (u32)(end - first);
-		g.key_bytes = bytes;
-		g.sorted_as = (ng == 1 && g.ncols == 1) ? cols[first].dtype : bytes <= 2 ? (u32)RSX_U16 : bytes <= 4 ? (u32)RSX_U32 : (u32)RSX_U64;
-	};
-	for (size_t ci = ncols; ci-- > 0;) {
-		const u32 w = (u32)dtype_size((int)cols[ci].dtype);
-		if (bytes && bytes + w > P) {
-			emit(ci + 1);
-			end = ci + 1;
-			bytes = 0;
-		}
-		bytes += w;
-	}
-	emit(0);
-	info->ngroups = ng;
-}
-
-// the kernel's descriptors of one group: the group's first column in the highest bits used
-LexArgs lex_args(const rsx_lex_col *cols, const rsx_lex_group &g, const void *perm)
-{
-	LexArgs a;
-	memset(&a, 0, sizeof(a));
-	a.ncols = g.ncols;
-	a.perm_vec = (((uintptr_t)perm) & 15) == 0;
-	u32 shift = 8 * g.key_bytes;
-	for (u32 j = 0; j < g.ncols; ++j) {
-		const rsx_lex_col &col = cols[g.first_col + j];
-		const u32 w = (u32)dtype_size((int)col.dtype);
-		shift -= 8 * w;
-		LexCol &d = a.col[j];
-		d.p = col.data;
-		d.wlog2 = w == 1 ? 0u : w == 2 ? 1u : w == 4 ? 2u : 3u;
-		d.shift = shift;
-		d.vec = (((uintptr_t)col.data) & (4 * w - 1)) == 0;
-		switch (w) {
-		case 1: { const KdfArgs<uint8_t> k = make_kdf<uint8_t>((int)col.dtype, (int)col.order); d.fmask = k.fmask; d.sflip = k.sflip; d.desc = k.desc; } break;
-		case 2: { const KdfArgs<uint16_t> k = make_kdf<uint16_t>((int)col.dtype, (int)col.order); d.fmask = k.fmask; d.sflip = k.sflip; d.desc = k.desc; } break;
-		case 4: { const KdfArgs<u32> k = make_kdf<u32>((int)col.dtype, (int)col.order); d.fmask = k.fmask; d.sflip = k.sflip; d.desc = k.desc; } break;
-		default: { const KdfArgs<u64> k = make_kdf<u64>((int)col.dtype, (int)col.order); d.fmask = k.fmask; d.sflip = k.sflip; d.desc = k.desc; } break;
-		}
-	}
-	return a;
-}
-
-// one group's keys packed (*cur == nullptr: group 0) or gathered through *cur, then sorted: group 0 by the rank sort, which
-// makes the permutation; every later group by the key + payload sort with the permutation as payload (*cur / *other: where it
-// is, and the second buffer of its sort)
-template <typename OT, typename IT>
-int lex_sort_group(Ctx &c, const rsx_lex_col *cols, const rsx_lex_group &g, size_t n, OT *k0, OT *k1, IT *base, IT *alt, IT **cur, IT **other,
-                   rsx_info *si)
-{
-	const LexArgs a = lex_args(cols, g, *cur);
-	const u64 quads = (u64)n / 4;
-	const dim3 grid((unsigned)std::max<u64>(1, std::min<u64>(LEX_MAX_GRID, (quads + LEX_THREADS - 1) / LEX_THREADS))), block(LEX_THREADS);
-	if (!*cur) {
-		hipLaunchKernelGGL((rsx_lex_pack_kernel<OT, u32, false>), grid, block, 0, c.stream, a, (const u32 *)nullptr, k0, (u64)n);
-		HIP_TRY(hipGetLastError());
-		void *res = nullptr;
-		RSX_TRY((sort_rank_device<OT, IT>(c, (const OT *)k0, base, n, (int)g.sorted_as, RSX_ASCENDING, &res, si)));
-		*cur = (IT *)res;
-		*other = *cur == base ? alt : base;
-		return RSX_OK;
-	}
-	hipLaunchKernelGGL((rsx_lex_pack_kernel<OT, IT, true>), grid, block, 0, c.stream, a, (const IT *)*cur, k0, (u64)n);
-	HIP_TRY(hipGetLastError());
-	RSX_TRY((sort_pairs_device<OT, IT>(c, k0, k1, *cur, *other, n, (int)g.sorted_as, RSX_ASCENDING, si)));
-	if (si->result_in_aux)
-		std::swap(*cur, *other);
-	return RSX_OK;
-}
-
-template <typename IT>
-int sort_lex_device(Ctx &c, const rsx_lex_col *cols, size_t n, IT *out, rsx_lex_info *info)
-{
-	// Buffers of this call's own, apart from everything the inner sorts use themselves (Ctx::keys, vals, seg, slack*, ...):
-	// [keys n][keys n] of the widest packed type, and indices [n][n][n] -- the rank sort of group 0 works in the first two
-	// (contiguous, as rsx_sort_rank_device wants them) and leaves the permutation in one of them; the second buffer of the
-	// key + payload sorts is the first one, or the third where the first holds the permutation (256-byte aligned both).
-	size_t widest = 0;
-	for (u32 gi = 0; gi < info->ngroups; ++gi) {
-		const rsx_lex_group &g = info->group[gi];
-		if (gi > 0 || g.ncols > 1)
-			widest = std::max<size_t>(widest, dtype_size((int)g.sorted_as));
-	}
-	const size_t kstride = (n * widest + 255) & ~(size_t)255, istride = (2 * n * sizeof(IT) + 255) & ~(size_t)255;
-	if (widest)
-		RSX_TRY(c.lexkeys.ensure(2 * kstride));
-	RSX_TRY(c.lexidx.ensure(istride + n * sizeof(IT)));
-	IT *base = (IT *)c.lexidx.p, *alt = (IT *)((char *)c.lexidx.p + istride), *cur = nullptr, *other = nullptr;
-	void *k0 = c.lexkeys.p, *k1 = (char *)c.lexkeys.p + kstride;
-	bool all_in_order = true;
-	for (u32 gi = 0; gi < info->ngroups; ++gi) {
-		rsx_lex_group &g = info->group[gi];
-		rsx_info si;
-		info_clear(&si, (int)g.sorted_as);
-		if (gi == 0 && g.ncols == 1) {
-			// a lone column: the rank sort on the caller's column itself, with its own type and order -- no copy, no kernel
-			const rsx_lex_col &col = cols[g.first_col];
-			void *res = nullptr;
-			int rc = RSX_EINVAL;
-			RSX_DISPATCH_KT((int)col.dtype, rc = (sort_rank_device<KT, IT>(c, (const KT *)col.data, base, n, (int)col.dtype, (int)col.order, &res, &si)));
-			RSX_TRY(rc);
-			cur = (IT *)res;
-			other = cur == base ? alt : base;
-		} else if (g.sorted_as == RSX_U16) {
-			RSX_TRY((lex_sort_group<uint16_t, IT>(c, cols, g, n, (uint16_t *)k0, (uint16_t *)k1, base, alt, &cur, &other, &si)));
-		} else if (g.sorted_as == RSX_U32) {
-			RSX_TRY((lex_sort_group<u32, IT>(c, cols, g, n, (u32 *)k0, (u32 *)k1, base, alt, &cur, &other, &si)));
-		} else {
-			RSX_TRY((lex_sort_group<u64, IT>(c, cols, g, n, (u64 *)k0, (u64 *)k1, base, alt, &cur, &other, &si)));
-		}
-		g.kept_cols = si.ncols;
-		g.hybrid = si.hybrid;
-		g.in_order = si.early_exit == 2;   // (the pre-sorted exit: group 0 has written 0 .. n-1, a later group left the permutation where it was)
-		all_in_order = all_in_order && g.in_order;
-	}
-	if (all_in_order)
-		info->early_exit = 2;
-	HIP_TRY(hipMemcpyAsync(out, cur, n * sizeof(IT), hipMemcpyDeviceToDevice, c.stream));
-	return RSX_OK;
-}
-
 }  // namespace
+
+#include "rsx_api.hpp"   // what the entry points share: dispatch by type, argument checks, host staging
 
 // =================================================================================
 // extern "C" surface
@@ -4472,9 +2995,7 @@ int rsx_sort_inplace_async(void *d_buf, void *d_scratch, size_t n, rsx_dtype dty
 		return fail(RSX_EINVAL, "rsx_sort_inplace_async: bad argument");
 	if (n < 2)
 		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
 	RSX_DISPATCH_KT(dtype, return sort_keys_inplace_async<KT>(*c, (KT *)d_buf, (KT *)d_scratch, n, dtype, order));
 	return RSX_OK;
@@ -4486,9 +3007,7 @@ int rsx_sort_inplace_async_hint(void *d_buf, void *d_scratch, size_t n, rsx_dtyp
 		return fail(RSX_EINVAL, "rsx_sort_inplace_async_hint: bad argument");
 	if (n < 2)
 		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
 	struct HintScope {   // (the sample kernel of the attempt enqueued by this call reads them: blind_enqueue)
 		Ctx &c;
@@ -4571,19 +3090,10 @@ int rsx_sort_pairs_inplace_async_ws(void *d_keys, void *d_keys_scratch, void *d_
 		return RSX_OK;
 	Ctx view;
 	size_t status_total = 0;
-	if (payload_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, status_total = (status_bytes<KT, u32>(n) * sizeof(KT)));
-	} else {
-		RSX_DISPATCH_KT(dtype, status_total = (status_bytes<KT, u64>(n) * sizeof(KT)));
-	}
+	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, status_total = (status_bytes<KT, VT>(n) * sizeof(KT)));
 	RSX_TRY(borrow_ctx(view, stream, d_workspace, workspace_bytes, n, kb, status_total));
-	if (payload_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_inplace_async<KT, u32>(view, (KT *)d_keys, (KT *)d_keys_scratch, (u32 *)d_vals,
-		                                                                 (u32 *)d_vals_scratch, n, dtype, order)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_inplace_async<KT, u64>(view, (KT *)d_keys, (KT *)d_keys_scratch, (u64 *)d_vals,
-		                                                                 (u64 *)d_vals_scratch, n, dtype, order)));
-	}
+	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_inplace_async<KT, VT>(view, (KT *)d_keys, (KT *)d_keys_scratch, (VT *)d_vals,
+	                                                                                     (VT *)d_vals_scratch, n, dtype, order)));
 	return RSX_OK;
 }
 
@@ -4622,17 +3132,10 @@ int rsx_sort_pairs_inplace_async(void *d_keys, void *d_keys_scratch, void *d_val
 		return fail(RSX_EINVAL, "rsx_sort_pairs_inplace_async: bad argument");
 	if (n < 2)
 		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
-	if (payload_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_inplace_async<KT, u32>(*c, (KT *)d_keys, (KT *)d_keys_scratch, (u32 *)d_vals,
-		                                                                 (u32 *)d_vals_scratch, n, dtype, order)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_inplace_async<KT, u64>(*c, (KT *)d_keys, (KT *)d_keys_scratch, (u64 *)d_vals,
-		                                                                 (u64 *)d_vals_scratch, n, dtype, order)));
-	}
+	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_inplace_async<KT, VT>(*c, (KT *)d_keys, (KT *)d_keys_scratch, (VT *)d_vals,
+	                                                                                     (VT *)d_vals_scratch, n, dtype, order)));
 	return RSX_OK;
 }
 
@@ -4648,9 +3151,7 @@ int rsx_sort_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, rsx_ord
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	RSX_DISPATCH_KT(dtype, return sort_keys_device<KT>(*c, (KT *)d_src, (KT *)d_aux, n, dtype, order, result, info));
 	return RSX_OK;
 }
@@ -4667,16 +3168,9 @@ int rsx_sort_pairs_device(void *d_keys, void *d_keys_aux, void *d_vals, void *d_
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	if (payload_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_device<KT, u32>(*c, (KT *)d_keys, (KT *)d_keys_aux, (u32 *)d_vals,
-		                                                         (u32 *)d_vals_aux, n, dtype, order, info)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_pairs_device<KT, u64>(*c, (KT *)d_keys, (KT *)d_keys_aux, (u64 *)d_vals,
-		                                                         (u64 *)d_vals_aux, n, dtype, order, info)));
-	}
+	RSX_LOCKED_CTX(c, stream);
+	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_device<KT, VT>(*c, (KT *)d_keys, (KT *)d_keys_aux, (VT *)d_vals,
+	                                                                              (VT *)d_vals_aux, n, dtype, order, info)));
 	return RSX_OK;
 }
 
@@ -4689,19 +3183,13 @@ int rsx_sort_rank_inplace_async(const void *d_src, void *d_index_buffer, size_t 
 		return fail(RSX_EINVAL, "rsx_sort_rank_inplace_async: n does not fit a 4-byte index");
 	if (n == 0)
 		return RSX_OK;                       // radix_sort_rank.hpp:28-32
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
 	if (n == 1) {
 		HIP_TRY(hipMemsetAsync(d_index_buffer, 0, idx_bytes, c->stream));
 		return RSX_OK;
 	}
-	if (idx_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_rank_inplace_async<KT, u32>(*c, (const KT *)d_src, (u32 *)d_index_buffer, n, dtype, order)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_rank_inplace_async<KT, u64>(*c, (const KT *)d_src, (u64 *)d_index_buffer, n, dtype, order)));
-	}
+	RSX_DISPATCH_KT_W(dtype, idx_bytes, IT, return (sort_rank_inplace_async<KT, IT>(*c, (const KT *)d_src, (IT *)d_index_buffer, n, dtype, order)));
 	return RSX_OK;
 }
 
@@ -4709,9 +3197,7 @@ int rsx_verify_poll(void *stream, uint64_t *mismatches)
 {
 	if (mismatches)
 		*mismatches = 0;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (!c->vasync.p)
 		return RSX_OK;
@@ -4732,9 +3218,7 @@ int rsx_async_route(void *stream, uint32_t *route)
 	if (!route)
 		return fail(RSX_EINVAL, "rsx_async_route: bad argument");
 	*route = 0;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	if (c->async_small)
 		return RSX_OK;   // (the one-launch sort writes no device-side plan: what lies there is an earlier sort's)
@@ -4772,22 +3256,15 @@ int rsx_sort_rank_device(const void *d_src, void *d_index_buffer, size_t n, rsx_
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	if (n == 1) {
 		HIP_TRY(hipMemsetAsync(d_index_buffer, 0, idx_bytes, c->stream));
 		if (info)
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	if (idx_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_rank_device<KT, u32>(*c, (const KT *)d_src, (u32 *)d_index_buffer, n, dtype,
-		                                                        order, result, info)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_rank_device<KT, u64>(*c, (const KT *)d_src, (u64 *)d_index_buffer, n, dtype,
-		                                                        order, result, info)));
-	}
+	RSX_DISPATCH_KT_W(dtype, idx_bytes, IT, return (sort_rank_device<KT, IT>(*c, (const KT *)d_src, (IT *)d_index_buffer, n, dtype, order,
+	                                                                         result, info)));
 	return RSX_OK;
 }
 
@@ -4809,9 +3286,7 @@ int rsx_sort(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order, v
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, nullptr);
 	if (is_device_ptr(src)) {
 		if (!is_device_ptr(aux))
 			return fail(RSX_EINVAL, "rsx_sort: src is a device pointer but aux is not");
@@ -4860,482 +3335,6 @@ int rsx_sort(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order, v
 	return RSX_OK;
 }
 
-/* ---- rsx_sort_unique: the distinct keys in order (rsx_unique.hpp) ---- */
-static int unique_args(const char *who, size_t n, rsx_dtype dtype, rsx_order order, const void *src, const void *aux, const void *counts,
-                       size_t count_bytes, void **result, size_t *n_unique)
-{
-	if (!dtype_size(dtype) || (order != RSX_ASCENDING && order != RSX_DESCENDING) || !result || !n_unique || (n && (!src || !aux)))
-		return fail(RSX_EINVAL, "%s: bad argument", who);
-	if (counts ? (count_bytes != 4 && count_bytes != 8) : (count_bytes != 0 && count_bytes != 4 && count_bytes != 8))
-		return fail(RSX_EINVAL, "%s: count_bytes = %zu (4 or 8)", who, count_bytes);
-	if (counts && count_bytes == 4 && (uint64_t)n > 0xFFFFFFFFull)
-		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte count", who, n);
-	return RSX_OK;
-}
-
-int rsx_sort_unique_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, rsx_order order, void *d_counts, size_t count_bytes,
-                           void *stream, void **result, size_t *n_unique, rsx_unique_info *info)
-{
-	rsx_unique_info local;
-	if (!info)
-		info = &local;
-	memset(info, 0, sizeof(*info));
-	info_clear(&info->sort, dtype);
-	RSX_TRY(unique_args("rsx_sort_unique_device", n, dtype, order, d_src, d_aux, d_counts, count_bytes, result, n_unique));
-	if (n < 2 && !(n == 1 && d_counts)) {
-		*result = d_src;
-		*n_unique = n;
-		info->sort.early_exit = 1;
-		return RSX_OK;
-	}
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess)
-		(void)hipGetLastError();
-	else if (st != hipStreamCaptureStatusNone)
-		return fail(RSX_EINVAL, "rsx_sort_unique_device: the stream is capturing (the call waits for the number of distinct keys)");
-	if (n == 1) {
-		// (one key, once: the only small case that has to write device memory)
-		const u64 one64 = 1;
-		const u32 one32 = 1;
-		HIP_TRY(hipMemcpyAsync(d_counts, count_bytes == 4 ? (const void *)&one32 : (const void *)&one64, count_bytes, hipMemcpyHostToDevice,
-		                       (hipStream_t)stream));
-		HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-		*result = d_src;
-		*n_unique = 1;
-		info->sort.early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_DISPATCH_KT(dtype, return sort_unique_device<KT>(*c, (KT *)d_src, (KT *)d_aux, n, dtype, order, d_counts, count_bytes, result,
-	                                                     n_unique, info));
-	return RSX_OK;
-}
-
-int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order, void *counts, size_t count_bytes, void **result,
-                    size_t *n_unique, rsx_unique_info *info)
-{
-	rsx_unique_info local;
-	if (!info)
-		info = &local;
-	memset(info, 0, sizeof(*info));
-	info_clear(&info->sort, dtype);
-	const size_t kb = dtype_size(dtype);
-	RSX_TRY(unique_args("rsx_sort_unique", n, dtype, order, src, aux, counts, count_bytes, result, n_unique));
-	if (n < 2 && !(n == 1 && counts)) {
-		*result = src;
-		*n_unique = n;
-		info->sort.early_exit = 1;
-		return RSX_OK;
-	}
-	if (n == 1 && rsx_device_count() <= 0) {
-		// (no device: every pointer is the host's)
-		if (count_bytes == 4)
-			*(uint32_t *)counts = 1;
-		else
-			*(uint64_t *)counts = 1;
-		*result = src;
-		*n_unique = 1;
-		info->sort.early_exit = 1;
-		return RSX_OK;
-	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	if (is_device_ptr(src)) {
-		if (!is_device_ptr(aux) || (counts && !is_device_ptr(counts)))
-			return fail(RSX_EINVAL, "rsx_sort_unique: src is a device pointer but aux or counts is not");
-		return rsx_sort_unique_device(src, aux, n, dtype, order, counts, count_bytes, nullptr, result, n_unique, info);
-	}
-	if (n == 1) {
-		if (count_bytes == 4)
-			*(uint32_t *)counts = 1;
-		else
-			*(uint64_t *)counts = 1;
-		*result = src;
-		*n_unique = 1;
-		info->sort.early_exit = 1;
-		return RSX_OK;
-	}
-	// host buffers: staged as rsx_sort stages them; the distinct keys (and counts) come back into the buffer that
-	// corresponds to the device buffer they ended in, the other one is left as it was
-	RSX_TRY(c->keys[0].ensure(n * kb));
-	RSX_TRY(c->keys[1].ensure(n * kb));
-	if (counts)
-		RSX_TRY(c->vals[0].ensure(n * count_bytes));
-	HIP_TRY(hipMemcpyAsync(c->keys[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	void *dres = nullptr;
-	RSX_TRY(rsx_sort_unique_device(c->keys[0].p, c->keys[1].p, n, dtype, order, counts ? c->vals[0].p : nullptr, count_bytes, nullptr, &dres,
-	                               n_unique, info));
-	void *hres = dres == c->keys[1].p ? aux : src;
-	if (dres == c->keys[1].p || info->route != RSX_UNIQUE_TRIVIAL)
-		HIP_TRY(hipMemcpyAsync(hres, dres, *n_unique * kb, hipMemcpyDeviceToHost, c->stream));
-	if (counts)
-		HIP_TRY(hipMemcpyAsync(counts, c->vals[0].p, *n_unique * count_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	*result = hres;
-	return RSX_OK;
-}
-
-/* ---- rsx_sort_topk: the first k of the sorted order (rsx_topk.hpp) ---- */
-static int topk_args(const char *who, const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_order order, const void *out_keys,
-                     const void *out_idx, size_t idx_bytes)
-{
-	if (!dtype_size(dtype) || (order != RSX_ASCENDING && order != RSX_DESCENDING) || (n && !src))
-		return fail(RSX_EINVAL, "%s: bad argument", who);
-	if (!out_keys && !out_idx)
-		return fail(RSX_EINVAL, "%s: both outputs are NULL", who);
-	if (idx_bytes != 4 && idx_bytes != 8)
-		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
-	if (idx_bytes == 4 && (uint64_t)n > (1ull << 32))
-		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
-	if (k > n)
-		return fail(RSX_EINVAL, "%s: k exceeds n (k = %zu, n = %zu)", who, k, n);
-	return RSX_OK;
-}
-
-int rsx_sort_topk_device(const void *d_src, size_t n, size_t k, rsx_dtype dtype, rsx_order order, void *d_out_keys, void *d_out_idx,
-                         size_t idx_bytes, void *stream, rsx_topk_info *info)
-{
-	rsx_topk_info local;
-	if (!info)
-		info = &local;
-	memset(info, 0, sizeof(*info));
-	info->key_bytes = (uint32_t)dtype_size(dtype);
-	RSX_TRY(topk_args("rsx_sort_topk_device", d_src, n, k, dtype, order, d_out_keys, d_out_idx, idx_bytes));
-	if (k == 0)
-		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess)
-		(void)hipGetLastError();
-	else if (st != hipStreamCaptureStatusNone)
-		return fail(RSX_EINVAL, "rsx_sort_topk_device: the stream is capturing (the call waits for what the selection found)");
-	if (n == 1) {
-		// (one key: itself, at index 0)
-		const size_t kb = dtype_size(dtype);
-		uint64_t key = 0;
-		HIP_TRY(hipMemcpyAsync(&key, d_src, kb, hipMemcpyDeviceToHost, c->stream));
-		if (d_out_keys)
-			HIP_TRY(hipMemcpyAsync(d_out_keys, d_src, kb, hipMemcpyDeviceToDevice, c->stream));
-		if (d_out_idx)
-			HIP_TRY(hipMemsetAsync(d_out_idx, 0, idx_bytes, c->stream));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		info->n_equal = 1;
-		info->kth_key = key;   // (little-endian: the low kb bytes)
-		return RSX_OK;
-	}
-	if (idx_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_topk_device<KT, u32>(*c, (const KT *)d_src, n, k, dtype, order, (KT *)d_out_keys, (u32 *)d_out_idx, info)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_topk_device<KT, u64>(*c, (const KT *)d_src, n, k, dtype, order, (KT *)d_out_keys, (u64 *)d_out_idx, info)));
-	}
-	return RSX_OK;
-}
-
-int rsx_sort_topk(const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_order order, void *out_keys, void *out_idx, size_t idx_bytes,
-                  rsx_topk_info *info)
-{
-	rsx_topk_info local;
-	if (!info)
-		info = &local;
-	memset(info, 0, sizeof(*info));
-	const size_t kb = dtype_size(dtype);
-	info->key_bytes = (uint32_t)kb;
-	RSX_TRY(topk_args("rsx_sort_topk", src, n, k, dtype, order, out_keys, out_idx, idx_bytes));
-	if (k == 0)
-		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	if (is_device_ptr(src)) {
-		if ((out_keys && !is_device_ptr(out_keys)) || (out_idx && !is_device_ptr(out_idx)))
-			return fail(RSX_EINVAL, "rsx_sort_topk: src is a device pointer but an output is not");
-		RSX_TRY(rsx_sort_topk_device(src, n, k, dtype, order, out_keys, out_idx, idx_bytes, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	// host buffers: the keys staged as rsx_sort_rank stages them, the k results brought back
-	const size_t kpad = (k * kb + 15) & ~(size_t)15;
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->tkout.ensure(kpad + k * idx_bytes));
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	char *dk = (char *)c->tkout.p, *di = dk + kpad;
-	RSX_TRY(rsx_sort_topk_device(c->recs[0].p, n, k, dtype, order, out_keys ? dk : nullptr, out_idx ? di : nullptr, idx_bytes, nullptr, info));
-	if (out_keys)
-		HIP_TRY(hipMemcpyAsync(out_keys, dk, k * kb, hipMemcpyDeviceToHost, c->stream));
-	if (out_idx)
-		HIP_TRY(hipMemcpyAsync(out_idx, di, k * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
-}
-
-/* ---- rsx_sort_nth: the elements at given ranks of the sorted order (rsx_nth.hpp) ---- */
-static int nth_args(const char *who, const void *src, size_t n, const uint64_t *ranks, size_t m, rsx_dtype dtype, rsx_order order,
-                    const void *out_keys, const void *out_idx, size_t idx_bytes)
-{
-	if (!dtype_size(dtype) || (order != RSX_ASCENDING && order != RSX_DESCENDING) || (n && !src))
-		return fail(RSX_EINVAL, "%s: bad argument", who);
-	if (!out_keys && !out_idx)
-		return fail(RSX_EINVAL, "%s: both outputs are NULL", who);
-	if (idx_bytes != 4 && idx_bytes != 8)
-		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
-	if (idx_bytes == 4 && (uint64_t)n > (1ull << 32))
-		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
-	if (m && !ranks)
-		return fail(RSX_EINVAL, "%s: ranks is NULL", who);
-	for (size_t j = 0; j < m; ++j)
-		if (ranks[j] >= (uint64_t)n)
-			return fail(RSX_EINVAL, "%s: rank exceeds n (ranks[%zu] = %llu, n = %zu)", who, j, (unsigned long long)ranks[j], n);
-	return RSX_OK;
-}
-
-static void nth_info_clear(rsx_nth_info *info, rsx_dtype dtype)
-{
-	memset(info, 0, sizeof(*info));
-	info->key_bytes = (uint32_t)dtype_size(dtype);
-}
-
-static void nth_fill_trivial(size_t m, uint64_t *n_less, uint64_t *n_equal)
-{
-	for (size_t j = 0; j < m; ++j) {
-		if (n_less)
-			n_less[j] = 0;
-		if (n_equal)
-			n_equal[j] = 1;
-	}
-}
-
-int rsx_sort_nth_device(const void *d_src, size_t n, const uint64_t *ranks, size_t m, rsx_dtype dtype, rsx_order order, void *d_out_keys,
-                        void *d_out_idx, size_t idx_bytes, uint64_t *n_less, uint64_t *n_equal, void *stream, rsx_nth_info *info)
-{
-	rsx_nth_info local;
-	if (!info)
-		info = &local;
-	nth_info_clear(info, dtype);
-	RSX_TRY(nth_args("rsx_sort_nth_device", d_src, n, ranks, m, dtype, order, d_out_keys, d_out_idx, idx_bytes));
-	if (m == 0)
-		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess)
-		(void)hipGetLastError();
-	else if (st != hipStreamCaptureStatusNone)
-		return fail(RSX_EINVAL, "rsx_sort_nth_device: the stream is capturing (the call waits for what the selection found)");
-	if (n == 1) {
-		// (one key: itself, at index 0, for every rank)
-		const dim3 grid((unsigned)std::min<u64>(1024, ((u64)m + 255) / 256));
-		if (idx_bytes == 4) {
-			RSX_DISPATCH_KT(dtype, hipLaunchKernelGGL((rsx_nth_single_kernel<KT, u32>), grid, dim3(256), 0, c->stream, (const KT *)d_src, (u64)m,
-			                                          (KT *)d_out_keys, (u32 *)d_out_idx));
-		} else {
-			RSX_DISPATCH_KT(dtype, hipLaunchKernelGGL((rsx_nth_single_kernel<KT, u64>), grid, dim3(256), 0, c->stream, (const KT *)d_src, (u64)m,
-			                                          (KT *)d_out_keys, (u64 *)d_out_idx));
-		}
-		HIP_TRY(hipGetLastError());
-		nth_fill_trivial(m, n_less, n_equal);
-		return RSX_OK;
-	}
-	NthAsk ask;
-	ask.ranks = ranks;
-	ask.m = m;
-	ask.n_less = n_less;
-	ask.n_equal = n_equal;
-	ask.distinct.assign(ranks, ranks + m);
-	std::sort(ask.distinct.begin(), ask.distinct.end());
-	ask.distinct.erase(std::unique(ask.distinct.begin(), ask.distinct.end()), ask.distinct.end());
-	ask.map.resize(m);
-	for (size_t j = 0; j < m; ++j)
-		ask.map[j] = (u32)std::min<size_t>(std::lower_bound(ask.distinct.begin(), ask.distinct.end(), ranks[j]) - ask.distinct.begin(),
-		                                   0xFFFFFFFFu);
-	if (idx_bytes == 4) {
-		RSX_DISPATCH_KT(dtype, return (sort_nth_device<KT, u32>(*c, (const KT *)d_src, n, ask, dtype, order, (KT *)d_out_keys, (u32 *)d_out_idx, info)));
-	} else {
-		RSX_DISPATCH_KT(dtype, return (sort_nth_device<KT, u64>(*c, (const KT *)d_src, n, ask, dtype, order, (KT *)d_out_keys, (u64 *)d_out_idx, info)));
-	}
-	return RSX_OK;
-}
-
-int rsx_sort_nth(const void *src, size_t n, const uint64_t *ranks, size_t m, rsx_dtype dtype, rsx_order order, void *out_keys, void *out_idx,
-                 size_t idx_bytes, uint64_t *n_less, uint64_t *n_equal, rsx_nth_info *info)
-{
-	rsx_nth_info local;
-	if (!info)
-		info = &local;
-	nth_info_clear(info, dtype);
-	const size_t kb = dtype_size(dtype);
-	RSX_TRY(nth_args("rsx_sort_nth", src, n, ranks, m, dtype, order, out_keys, out_idx, idx_bytes));
-	if (m == 0)
-		return RSX_OK;
-	auto one_on_host = [&]() {
-		for (size_t j = 0; j < m; ++j) {
-			if (out_keys)
-				memcpy((char *)out_keys + j * kb, src, kb);
-			if (out_idx)
-				memset((char *)out_idx + j * idx_bytes, 0, idx_bytes);
-		}
-		nth_fill_trivial(m, n_less, n_equal);
-	};
-	if (n == 1 && rsx_device_count() <= 0) {
-		// (no device: every pointer is the host's)
-		one_on_host();
-		return RSX_OK;
-	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	if (is_device_ptr(src)) {
-		if ((out_keys && !is_device_ptr(out_keys)) || (out_idx && !is_device_ptr(out_idx)))
-			return fail(RSX_EINVAL, "rsx_sort_nth: src is a device pointer but an output is not");
-		RSX_TRY(rsx_sort_nth_device(src, n, ranks, m, dtype, order, out_keys, out_idx, idx_bytes, n_less, n_equal, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	if (n == 1) {
-		one_on_host();
-		return RSX_OK;
-	}
-	// host buffers: the keys staged as rsx_sort_rank stages them, the m results brought back
-	const size_t mpad = (m * kb + 15) & ~(size_t)15;
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->nthout.ensure(mpad + m * idx_bytes));
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	char *dk = (char *)c->nthout.p, *di = dk + mpad;
-	RSX_TRY(rsx_sort_nth_device(c->recs[0].p, n, ranks, m, dtype, order, out_keys ? dk : nullptr, out_idx ? di : nullptr, idx_bytes, n_less,
-	                            n_equal, nullptr, info));
-	if (out_keys)
-		HIP_TRY(hipMemcpyAsync(out_keys, dk, m * kb, hipMemcpyDeviceToHost, c->stream));
-	if (out_idx)
-		HIP_TRY(hipMemcpyAsync(out_idx, di, m * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
-}
-
-/* ---- rsx_sort_lex: stable argsort by several key columns (rsx_lex.hpp) ---- */
-static int lex_args_check(const char *who, const rsx_lex_col *cols, size_t ncols, size_t n, const void *out_idx, size_t idx_bytes)
-{
-	if (!cols)
-		return fail(RSX_EINVAL, "%s: cols is NULL", who);
-	if (ncols == 0 || ncols > RSX_LEX_MAX_COLS)
-		return fail(RSX_EINVAL, "%s: ncols = %zu (1 .. %d columns)", who, ncols, (int)RSX_LEX_MAX_COLS);
-	for (size_t i = 0; i < ncols; ++i) {
-		if (!dtype_size((int)cols[i].dtype))
-			return fail(RSX_EINVAL, "%s: column %zu: unknown dtype %u", who, i, cols[i].dtype);
-		if (cols[i].order != RSX_ASCENDING && cols[i].order != RSX_DESCENDING)
-			return fail(RSX_EINVAL, "%s: column %zu: unknown order %u", who, i, cols[i].order);
-		if (n && !cols[i].data)
-			return fail(RSX_EINVAL, "%s: column %zu is NULL", who, i);
-	}
-	if (idx_bytes != 4 && idx_bytes != 8)
-		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
-	if (n && !out_idx)
-		return fail(RSX_EINVAL, "%s: the output is NULL", who);
-	if (idx_bytes == 4 && (uint64_t)n > (1ull << 32))
-		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
-	return RSX_OK;
-}
-
-static void lex_info_clear(rsx_lex_info *info, size_t ncols, size_t n)
-{
-	memset(info, 0, sizeof(*info));
-	info->ncols = (uint32_t)std::min<size_t>(ncols, RSX_LEX_MAX_COLS);
-	info->pack_bytes = env().lex_pack_bytes;
-	info->early_exit = n < 2 ? 1 : 0;
-}
-
-int rsx_sort_lex_device(const rsx_lex_col *cols, size_t ncols, size_t n, void *d_out_idx, size_t idx_bytes, void *stream, rsx_lex_info *info)
-{
-	rsx_lex_info local;
-	if (!info)
-		info = &local;
-	lex_info_clear(info, ncols, n);
-	RSX_TRY(lex_args_check("rsx_sort_lex_device", cols, ncols, n, d_out_idx, idx_bytes));
-	if (n == 0)
-		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-	if (hipStreamIsCapturing((hipStream_t)stream, &st) != hipSuccess)
-		(void)hipGetLastError();
-	else if (st != hipStreamCaptureStatusNone)
-		return fail(RSX_EINVAL, "rsx_sort_lex_device: the stream is capturing (the call waits between its sorts)");
-	if (n == 1) {
-		HIP_TRY(hipMemsetAsync(d_out_idx, 0, idx_bytes, c->stream));
-		return RSX_OK;
-	}
-	lex_plan(cols, ncols, info->pack_bytes, info);
-	if (idx_bytes == 4)
-		return sort_lex_device<u32>(*c, cols, n, (u32 *)d_out_idx, info);
-	return sort_lex_device<u64>(*c, cols, n, (u64 *)d_out_idx, info);
-}
-
-int rsx_sort_lex(const rsx_lex_col *cols, size_t ncols, size_t n, void *out_idx, size_t idx_bytes, rsx_lex_info *info)
-{
-	rsx_lex_info local;
-	if (!info)
-		info = &local;
-	lex_info_clear(info, ncols, n);
-	RSX_TRY(lex_args_check("rsx_sort_lex", cols, ncols, n, out_idx, idx_bytes));
-	if (n == 0)
-		return RSX_OK;
-	if (n == 1 && rsx_device_count() <= 0) {
-		// (no device: every pointer is the host's)
-		memset(out_idx, 0, idx_bytes);
-		return RSX_OK;
-	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
-	const bool dev = is_device_ptr(out_idx);
-	for (size_t i = 0; i < ncols; ++i)
-		if (is_device_ptr(cols[i].data) != dev)
-			return fail(RSX_EINVAL, "rsx_sort_lex: host and device pointers are mixed (column %zu and the output)", i);
-	if (dev) {
-		RSX_TRY(rsx_sort_lex_device(cols, ncols, n, out_idx, idx_bytes, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	if (n == 1) {
-		memset(out_idx, 0, idx_bytes);
-		return RSX_OK;
-	}
-	// host buffers: every DISTINCT column staged once, each on a 256-byte boundary; the n indices brought back
-	rsx_lex_col dcols[RSX_LEX_MAX_COLS];
-	size_t off[RSX_LEX_MAX_COLS], total = 0;
-	bool staged_here[RSX_LEX_MAX_COLS];
-	for (size_t i = 0; i < ncols; ++i) {
-		const size_t w = dtype_size((int)cols[i].dtype);
-		size_t j = 0;
-		while (j < i && !(cols[j].data == cols[i].data && dtype_size((int)cols[j].dtype) == w))
-			++j;
-		staged_here[i] = j == i;
-		if (j < i) {
-			off[i] = off[j];
-		} else {
-			off[i] = total;
-			total += (n * w + 255) & ~(size_t)255;
-		}
-	}
-	RSX_TRY(c->lexstage.ensure(total + n * idx_bytes));
-	char *stage = (char *)c->lexstage.p;
-	for (size_t i = 0; i < ncols; ++i) {
-		dcols[i] = cols[i];
-		dcols[i].data = stage + off[i];
-		if (staged_here[i])
-			HIP_TRY(hipMemcpyAsync(stage + off[i], cols[i].data, n * dtype_size((int)cols[i].dtype), hipMemcpyHostToDevice, c->stream));
-	}
-	RSX_TRY(rsx_sort_lex_device(dcols, ncols, n, stage + total, idx_bytes, nullptr, info));
-	HIP_TRY(hipMemcpyAsync(out_idx, stage + total, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
-}
-
 int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype, size_t idx_bytes, rsx_order order,
                   void **result, rsx_info *info)
 {
@@ -5352,9 +3351,7 @@ int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, nullptr);
 	const bool dev = is_device_ptr(src);
 	if (dev != is_device_ptr(index_buffer))
 		return fail(RSX_EINVAL, "rsx_sort_rank: src and index_buffer must both be host or both be device pointers");
@@ -5423,6 +3420,16 @@ int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype
 	return RSX_OK;
 }
 
+}  // extern "C"
+
+// one file per feature: its host driver (anonymous namespace) and its entry points (extern "C")
+#include "rsx_unique_api.hpp"    // rsx_sort_unique[_device]
+#include "rsx_topk_api.hpp"      // rsx_sort_topk[_device]
+#include "rsx_nth_api.hpp"       // rsx_sort_nth[_device]
+#include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
+
+extern "C" {
+
 #include "rsx_records.hpp"       // rsx_sort_rank_keys, rsx_sort_records, rsx_sort_records_tagged[_device]
 
 #include "rsx_multi_entry.hpp"   // rsx_sort_multi
@@ -5433,9 +3440,7 @@ int rsx_histogram_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_order
 	const size_t kb = dtype_size(dtype);
 	if (!kb || !d_hist || !d_unsorted || (n && !d_src))
 		return fail(RSX_EINVAL, "rsx_histogram_device: bad argument");
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	HIP_TRY(hipMemsetAsync(d_hist, 0, 256 * kb * sizeof(u64), c->stream));
 	HIP_TRY(hipMemsetAsync(d_unsorted, 0, sizeof(u32), c->stream));
 	if (n == 0)
@@ -5463,9 +3468,7 @@ int rsx_msd_split_device(const void *d_src, void *d_dst, size_t n, rsx_dtype dty
 		top_hist[i] = 0;
 	if (n == 0)
 		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	const size_t hist_bytes = kb * 256 * sizeof(u64);
 	HIP_TRY(hipMemsetAsync(c->ghist(), 0, hist_bytes, c->stream));
 	HIP_TRY(hipMemsetAsync(c->small_set(), 0, 256, c->stream));
@@ -5485,9 +3488,7 @@ int rsx_msd_split_async(const void *d_src, void *d_dst, size_t n, rsx_dtype dtyp
 	const u32 col = column < 0 ? (u32)kb - 1 : (u32)column;
 	if (n == 0)
 		return RSX_OK;
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
 	HIP_TRY(hipMemsetAsync(c->small_set(), 0, 256, c->stream));
 	RSX_DISPATCH_KT(dtype, return msd_split_known<KT>(*c, (const KT *)d_src, (KT *)d_dst, n, dtype, order, col, (const u64 *)d_hist, hot));
@@ -5560,9 +3561,7 @@ int rsx_fill_splitmix_device(void *d_dst, size_t n, size_t elem_bytes, uint64_t 
 {
 	if (n && !d_dst)
 		return fail(RSX_EINVAL, "rsx_fill_splitmix_device: null destination");
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	if (n == 0)
 		return RSX_OK;
 	const dim3 grid(2048), block(256);

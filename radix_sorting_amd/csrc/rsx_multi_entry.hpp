@@ -1,5 +1,5 @@
 // rsx_multi_entry.hpp: rsx_sort_multi (inside rsx.hip's extern "C" block) -- part of librsx.so's host side; included by rsx.hip at the point where it used to stand (one translation unit:
-// the kernels' instantiations are shared).  See rsx.hip for the context type, the error convention and the helpers used here.
+// the kernels' instantiations are shared).  See rsx_ctx.hpp for the context type and the error convention, rsx_api.hpp for what the entry points share.
 #pragma once
 
 // radix_sort(src, aux, n) on host buffers with the work spread over several devices of ONE process (SURVEY.md 8b item 5;

@@ -1,5 +1,5 @@
 // rsx_multi_state.hpp: the per-rank state and helpers of rsx_sort_multi (inside rsx.hip's anonymous namespace) -- part of librsx.so's host side; included by rsx.hip at the point where it used to stand (one translation unit:
-// the kernels' instantiations are shared).  See rsx.hip for the context type, the error convention and the helpers used here.
+// the kernels' instantiations are shared).  See rsx_ctx.hpp for the context type and the error convention, rsx_api.hpp for what the entry points share.
 #pragma once
 
 // ---- single-process multi-device sort (rsx_sort_multi) -----------------------------------------------------------------

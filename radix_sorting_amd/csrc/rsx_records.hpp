@@ -1,6 +1,6 @@
 // rsx_records.hpp: sorts of records -- opaque keys from the host (rsx_sort_rank_keys, rsx_sort_records) and a declared key
 // field (rsx_sort_records_tagged[_device]); inside rsx.hip's extern "C" block -- part of librsx.so's host side; included by rsx.hip at the point where it used to stand (one translation unit:
-// the kernels' instantiations are shared).  See rsx.hip for the context type, the error convention and the helpers used here.
+// the kernels' instantiations are shared).  See rsx_ctx.hpp for the context type and the error convention, rsx_api.hpp for what the entry points share.
 #pragma once
 
 int rsx_sort_rank_keys(const void *keys, size_t key_bytes, void *index_buffer, size_t n, size_t idx_bytes, void **result,
@@ -37,9 +37,7 @@ int rsx_sort_records(void *src, void *aux, size_t n, size_t rec_bytes, const voi
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, nullptr);
 	const size_t wide = n > (1ull << 32) ? 8 : 4;
 	RSX_TRY(c->keys[0].ensure(n * key_bytes));   // note: rank passes use keys[0]/keys[1] too; the uploaded keys live in recs[1]
 	RSX_TRY(c->recs[1].ensure(n * key_bytes > n * rec_bytes ? n * key_bytes : n * rec_bytes));
@@ -162,9 +160,7 @@ int rsx_sort_records_tagged_device(void *d_src, void *d_aux, size_t n, size_t re
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(stream, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, stream);
 	rsx_info li;
 	RSX_TRY(records_tagged_core(*c, d_src, d_aux, n, rec_bytes, key_offset, key_dtype, order, &li));
 	if (info)
@@ -189,9 +185,7 @@ int rsx_sort_records_tagged(void *src, void *aux, size_t n, size_t rec_bytes, si
 			info->early_exit = 1;
 		return RSX_OK;
 	}
-	Ctx *c;
-	RSX_TRY(get_ctx(nullptr, &c));
-	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu);
+	RSX_LOCKED_CTX(c, nullptr);
 	RSX_TRY(c->recs[0].ensure(n * rec_bytes));
 	RSX_TRY(c->recs[1].ensure(n * rec_bytes));
 	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * rec_bytes, hipMemcpyHostToDevice, c->stream));

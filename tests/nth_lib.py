@@ -16,7 +16,7 @@ def tile(kb):
 
 
 def capacity(n):
-    """The candidate buffer's capacity (radix_sorting_amd/csrc/rsx.hip, nth_cap): active buckets that together hold more stay
+    """The candidate buffer's capacity (radix_sorting_amd/csrc/rsx_nth_api.hpp, nth_cap): active buckets that together hold more stay
     in the input for another digit."""
     return n // 8 + 1024
 

@@ -1,6 +1,6 @@
 """The stability guard: ranking by returning LDS atomics rests on gfx950 handing the lanes of one
 instruction that hit the same cell their values in lane order.  Guarded by (1) a device self-check in two shapes when a
-context is created (rsx.hip, lds_order_selfcheck: 8 waves of bare atomics and the production shape of 16 waves with
+context is created (rsx_ctx.hpp, lds_order_selfcheck: 8 waves of bare atomics and the production shape of 16 waves with
 staging traffic), (2) RSX_VERIFY=1, which re-ranks one tile of every host-scheduled scatter pass without LDS atomics and
 fails the call on any difference, and (3) this soak: 20 s of back-to-back sorts whose outputs are checked."""
 import os

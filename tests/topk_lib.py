@@ -15,7 +15,7 @@ def tile(kb):
 
 
 def capacity(n):
-    """The candidate buffer's capacity (radix_sorting_amd/csrc/rsx.hip, topk_cap): a larger selected bucket stays in the input."""
+    """The candidate buffer's capacity (radix_sorting_amd/csrc/rsx_topk_api.hpp, topk_cap): a larger selected bucket stays in the input."""
     return n // 8 + 1024
 
 
