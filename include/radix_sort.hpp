@@ -293,6 +293,30 @@ T *radix_sort_unique(T *RESTRICT src, T *RESTRICT aux, size_t n, size_t *n_uniqu
 	return static_cast<T *>(result);
 }
 
+// Not in the reference's header (the same README section one step further): for every element of src, which is not written,
+// the index of its group among the distinct elements in order of kf(element) into inverse (room for n; may be nullptr) --
+// what np.unique(return_inverse=True) returns, by bit pattern.  If given (room for n each): the distinct elements into keys,
+// how many of each into counts, the smallest index of each into first.  Returns the number of groups (rsx_sort_group).
+// Scalar T with basic_kdfs::kdf or rsx_kdf::descending<T>.
+template <typename T, typename IdxType = uint32_t, typename KeyFunc = decltype(basic_kdfs::kdf<T>)>
+size_t radix_sort_group(const T *src, IdxType *inverse, size_t n, T *keys = nullptr, IdxType *counts = nullptr, IdxType *first = nullptr,
+                        KeyFunc &&kf = basic_kdfs::kdf<T>)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, KeyFunc> || rsx_detail::is_descending_kdf_v<T, KeyFunc>,
+	              "radix_sort_group takes scalar keys with basic_kdfs::kdf or rsx_kdf::descending");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_group: IdxType of 4 or 8 bytes");
+	if constexpr (rsx_detail::may_be_default_kdf_v<T, KeyFunc>)
+		if (!rsx_detail::kdf_kind<T, KeyFunc>::is_default(kf))
+			throw std::invalid_argument("radix_sort_group: a function other than basic_kdfs::kdf<T> was passed as KeyFunc");
+	size_t n_groups = 0;
+	const int rc = rsx_sort_group(src, n, rsx_detail::dtype_of<T>(),
+	                              rsx_detail::is_descending_kdf_v<T, KeyFunc> ? RSX_DESCENDING : RSX_ASCENDING, inverse, keys, counts, first,
+	                              sizeof(IdxType), &n_groups, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_group", rc);
+	return n_groups;
+}
+
 // Not in the reference's header (its README's "Hybrids" note): the first k elements of the stable sorted order of src, which
 // is not written, into out (room for k), and their positions in src into idx if given (room for k; equal keys in ascending
 // index order, as radix_sort_rank orders them).  Returns k.  Scalar T with basic_kdfs::kdf; RSX_DESCENDING for the

@@ -128,6 +128,9 @@
  *   RSX_UNIQUE_MAX_BITS=k   rsx_sort_unique*: the widest bitmap is 2^k bits (default 24, at most 30); 0: never a bitmap or a
  *                           count table -- everything but all-equal keys goes through the sort and one compaction (tests
  *                           force that route with it, tools/unique_probe.py sweeps the cut-off);
+ *   RSX_GROUP_MAX_BITS=k    rsx_sort_group*: the widest bitmap under the rank cells is 2^k bits (default 24, at most 30); 0: never
+ *                           a bitmap, cells or a count table -- everything but all-equal keys goes through the sort and the
+ *                           heads pass (tests force that route with it, tools/group_probe.py sweeps the cut-off);
  *   RSX_TOPK_FORCE=1        rsx_sort_topk*: the select route whenever n >= 2 and 0 < k <= n; =2: always the sort route
  *                           (tests run both and compare; tools/topk_probe.py times both);
  *   RSX_NTH_FORCE=1         rsx_sort_nth*: the select route whenever n >= 2 and 1 <= distinct ranks <= RSX_NTH_MAX_SELECT_RANKS;
@@ -366,6 +369,53 @@ int rsx_sort_unique_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, 
 int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order,
                     void *counts, size_t count_bytes,
                     void **result, size_t *n_unique, rsx_unique_info *info);
+
+/* ---- dense group ids of the keys: the inverse of rsx_sort_unique (a rank directory over its bitmap) -------- */
+
+/* For every key the index of its group among the distinct keys in order, and optionally the groups themselves.
+ * Let U[0 .. G) be what rsx_sort_unique returns for the same keys, dtype and order: the distinct BIT PATTERNS, ascending by
+ * kdf(key) (RSX_DESCENDING: by the complemented KDF) -- -0.0 and +0.0 are two groups, NaNs with different payloads too.
+ *   - *n_groups = G; out_inverse[i], i < n, is the j with U[j] bit-equal to src[i]; out_keys[j] = U[j], out_counts[j] = the
+ *     number of elements of group j, out_first[j] = the smallest i with out_inverse[i] == j, for j < G.
+ *   - Buffers: d_src is never written.  Every output may be NULL, each on its own; n_groups is required.  Each output has
+ *     room for n elements and nothing outside [0, n) of any of them is touched; entries of keys, counts and first at or
+ *     past G are unspecified.  idx_bytes is 4 or 8 and applies to inverse, counts and first; with 4, n must fit, or the call
+ *     fails with RSX_EINVAL "does not fit".
+ *   - Errors: bad dtype, order or idx_bytes, NULL n_groups, n && !src: RSX_EINVAL.  n == 0: RSX_OK, *n_groups = 0, nothing
+ *     written, no device needed.  n == 1: rsx_sort_group on host pointers needs no device (it writes 0, src[0], 1, 0),
+ *     rsx_sort_group_device only for the stores.  Otherwise, without a GPU: RSX_ENODEVICE, nothing written.  A capturing
+ *     stream: RSX_EINVAL (the call waits for the number of groups).  A failed allocation of the bitmap or the cells is not
+ *     an error: the call takes the sort route.
+ *   - Blocking: the call returns once *n_groups is on the host; the device outputs are valid for work ordered after it on
+ *     `stream`.
+ * The route is chosen from what the call can observe of the keys (rsx_group_info.route).  Where at most
+ * RSX_GROUP_MAX_BITS bits of the derived keys vary and neither counts nor first are wanted, rsx_sort_unique's bitmap is
+ * made, one 8-byte cell per word of it holds the word and the number of set bits below it, and every key looks its group
+ * up with one load and one popcount: two streaming passes over the keys and no sort.  Where one byte column varies (all
+ * 1-byte keys) the cells come from the plan's 256 counts, which are the groups' counts as well.  Everything else -- first
+ * indices always -- is a stable key + index sort of a workspace copy (rsx_sort_pairs_device's routes; none where the input
+ * is sorted already) and one pass over its result that numbers the head flags and scatters through the permutation.
+ * Memory, in the (device, stream) context: the bitmap and its cells (at most 12 bytes per 32 packed values: 6 MiB at the
+ * default cut-off), or a copy of the keys, its second buffer and 2 n indices; freed by rsx_release / rsx_release_stream. */
+enum { RSX_GROUP_TRIVIAL = 0,      /* n < 2, or every key equal                                          */
+       RSX_GROUP_RANK_LDS = 1,     /* bitmap + rank cells, the lookup reads the cells from LDS           */
+       RSX_GROUP_RANK_GLOBAL = 2,  /* the same, cells read from device memory (L2)                       */
+       RSX_GROUP_TABLE = 3,        /* one kept column: cells made from the plan's 256 counts, no mark pass */
+       RSX_GROUP_SORT = 4 };       /* stable key + index sort (any route), heads, scan, scatter          */
+typedef struct rsx_group_info {
+	rsx_info sort;          /* as rsx_unique_info.sort */
+	uint32_t route;         /* RSX_GROUP_* */
+	uint32_t varying_bits;  /* popcount of the KDF bits that differ among the keys; 0 = not computed */
+	uint64_t table_bytes;   /* bitmap + cells used, 0 otherwise */
+} rsx_group_info;
+
+int rsx_sort_group_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_order order,
+                          void *d_out_inverse, void *d_out_keys, void *d_out_counts, void *d_out_first,
+                          size_t idx_bytes, void *stream, size_t *n_groups, rsx_group_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind) */
+int rsx_sort_group(const void *src, size_t n, rsx_dtype dtype, rsx_order order,
+                   void *out_inverse, void *out_keys, void *out_counts, void *out_first,
+                   size_t idx_bytes, size_t *n_groups, rsx_group_info *info);
 
 /* ---- the first k of the sorted order ("Hybrids", README.md:647-650: one MSB pass, then only the sub-result that matters) -- */
 

@@ -57,6 +57,15 @@ class UniqueInfo(C.Structure):
     _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
 
 
+# rsx_group_info.route
+GROUP_TRIVIAL, GROUP_RANK_LDS, GROUP_RANK_GLOBAL, GROUP_TABLE, GROUP_SORT = range(5)
+
+
+class GroupInfo(C.Structure):
+    """rsx_group_info: the route rsx_sort_group* took and what the front half of the sort decided."""
+    _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
+
+
 # rsx_topk_info.route
 TOPK_TRIVIAL, TOPK_SELECT, TOPK_SORT = range(3)
 
@@ -106,6 +115,7 @@ _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
 _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 _PTINFO = C.POINTER(TopkInfo)
+_PGINFO = C.POINTER(GroupInfo)
 _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 ABI = [
@@ -129,6 +139,8 @@ ABI = [
     ("rsx_sort_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _PVP, _PINFO]),
     ("rsx_sort_unique_device", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _VP, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
+    ("rsx_sort_group_device", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP, _PSZ, _PGINFO]),
+    ("rsx_sort_group", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _PSZ, _PGINFO]),
     ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
     ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
     ("rsx_sort_nth_device", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _VP, _PNINFO]),
@@ -318,6 +330,49 @@ def radix_sort_unique(src, aux, dtype=None, order=ASCENDING, counts=None, stream
                                        C.byref(res), C.byref(nu), C.byref(info)))
     out = aux if (src.numel() and res.value == aux.data_ptr() and res.value != src.data_ptr()) else src
     return out[:nu.value], (None if counts is None else counts[:nu.value]), info
+
+
+def radix_sort_group(src, dtype=None, order=ASCENDING, idx_dtype=None, keys=False, counts=False, first=False, stream=None,
+                     inverse=True):
+    """rsx_sort_group_device: for every key of ``src`` (not written) the index of its group among the distinct keys in order
+    of kdf(key) -- what ``torch.unique(sorted=True, return_inverse=True)`` calls the inverse, by BIT PATTERN (-0.0 and +0.0
+    are two groups).
+
+    Returns (inverse, keys[:G] or None, counts[:G] or None, first[:G] or None, info): ``keys`` are radix_sort_unique's,
+    ``counts[j]`` the size of group j, ``first[j]`` the smallest index whose key is ``keys[j]``.  ``keys`` / ``counts`` /
+    ``first`` / ``inverse``: True allocates the output (n elements; ``idx_dtype``, default torch.int32, for the three index
+    arrays), False leaves it out, a device tensor with room for n elements is written in place.  Asking for counts or first
+    gives up the sort-free routes except the one-column table (first: that one too).  The call returns once G is known."""
+    import torch
+    _check_dev(src)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    n = src.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+
+    def buf(want, what, dt, size):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(n, dtype=dt, device=src.device)
+        _check_dev(want)
+        if want.numel() < n or want.element_size() != size:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    inv = buf(inverse, "inverse", idx_dtype, idx_bytes)
+    k = buf(keys, "keys", src.dtype, src.element_size())
+    cn = buf(counts, "counts", idx_dtype, idx_bytes)
+    fi = buf(first, "first", idx_dtype, idx_bytes)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    ng, info = C.c_size_t(0), GroupInfo()
+    check(lib().rsx_sort_group_device(src.data_ptr(), n, code, order, ptr(inv), ptr(k), ptr(cn), ptr(fi), idx_bytes,
+                                      _stream_ptr(stream), C.byref(ng), C.byref(info)))
+    g = ng.value
+    cut = lambda t: None if t is None else t[:g]
+    return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
 
 
 def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
@@ -635,6 +690,36 @@ def radix_sort_unique_host(src, aux, dtype, order=ASCENDING, counts=None):
                                 C.byref(info)))
     out = aux if (src.size and res.value == aux.ctypes.data and res.value != src.ctypes.data) else src
     return out[:nu.value], (None if counts is None else counts[:nu.value]), info
+
+
+def radix_sort_group_host(src, dtype, order=ASCENDING, idx_dtype=None, keys=False, counts=False, first=False, inverse=True):
+    """rsx_sort_group on a host numpy buffer; returns (inverse, keys[:G] or None, counts[:G] or None, first[:G] or None, info)
+    as radix_sort_group does (``idx_dtype``: a 4- or 8-byte numpy integer type, default uint32; an output may also be given
+    as a numpy array with room for n elements)."""
+    import numpy as np
+    if src.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src does not match the key type")
+    n = src.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+
+    def buf(want, what, dt):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(n, dtype=dt)
+        if want.size < n or want.itemsize != np.dtype(dt).itemsize:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    inv, k = buf(inverse, "inverse", idx_dtype), buf(keys, "keys", src.dtype)
+    cn, fi = buf(counts, "counts", idx_dtype), buf(first, "first", idx_dtype)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    ng, info = C.c_size_t(0), GroupInfo()
+    check(lib().rsx_sort_group(src.ctypes.data, n, dtype, order, ptr(inv), ptr(k), ptr(cn), ptr(fi), idx_dtype.itemsize,
+                               C.byref(ng), C.byref(info)))
+    g = ng.value
+    cut = lambda a: None if a is None else a[:g]
+    return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
 
 
 def radix_sort_topk_host(src, k, dtype, order=ASCENDING, want_idx=True, idx_dtype=None):

@@ -198,6 +198,8 @@ struct Ctx {
 	DevBuf logslots;    // ... the level-2 slots (four bytes per key)
 	DevBuf ubits;       // rsx_sort_unique*: the bitmap, one bit per packed value (at most 2^RSX_UNIQUE_MAX_BITS / 8 bytes)
 	DevBuf urecs;       // ... [8 u64: sample / totals][UniqueRec per chunk of the bitmap or tile of the sorted array]
+	DevBuf gcells;      // rsx_sort_group*: one GroupCell per word of the bitmap in ubits: the word and the set bits below it
+	DevBuf gout;        // ... rsx_sort_group on host buffers: the staged outputs
 	DevBuf tkctl;       // rsx_sort_topk*: [TopkCtl][rows of the input's ranges][rows of the candidates'][their offsets]
 	DevBuf tkpairs;     // ... the k (key, index) pairs and the second buffers of their sort: [keys k][keys k][indices k][indices k]
 	DevBuf tkcand;      // ... the selected bucket's (key, index) candidates: [keys cap][indices cap], cap = n / 8 + 1024
@@ -305,6 +307,8 @@ struct Ctx {
 		logslots.release();
 		ubits.release();
 		urecs.release();
+		gcells.release();
+		gout.release();
 		tkctl.release();
 		tkpairs.release();
 		tkcand.release();

@@ -16,6 +16,8 @@ namespace {
 std::atomic<uint32_t> g_env_epoch{0};   // bumped by rsx_reload_env()
 // rsx_sort_unique*: the widest bitmap the library was compiled for, and the widest it takes by default
 enum : unsigned { UNIQUE_MAX_BITS_COMPILED = 30, UNIQUE_MAX_BITS_DEFAULT = 24 };
+// rsx_sort_group*: the same for the bitmap its rank cells stand on
+enum : unsigned { GROUP_MAX_BITS_COMPILED = 30, GROUP_MAX_BITS_DEFAULT = 24 };
 // rsx_sort_lex*: neighbouring columns are packed into one key of at most this many bytes
 enum : unsigned { LEX_PACK_BYTES_DEFAULT = 4 };
 struct Env {
@@ -72,6 +74,7 @@ struct Env {
 	bool pairs_leaf_big = false;     // RSX_PAIRS_LEAF_BIG=1 (tests): key + payload and rank sorts without a histogram: the leaves' shape for 10240 pairs at every size
 	unsigned log_min_log2 = 0;       // RSX_LOG_MIN_LOG2: ... from 2^this keys on (tests: 20; default: from 24 Mi keys)
 	unsigned unique_max_bits = UNIQUE_MAX_BITS_DEFAULT;   // RSX_UNIQUE_MAX_BITS=k: rsx_sort_unique*: the widest bitmap is 2^k bits (0: never a bitmap or a table; at most 30)
+	unsigned group_max_bits = GROUP_MAX_BITS_DEFAULT;     // RSX_GROUP_MAX_BITS=k: rsx_sort_group*: the widest bitmap under the rank cells is 2^k bits (0: never a bitmap, cells or a table; at most 30)
 	unsigned nth_force = 0;          // RSX_NTH_FORCE=1: rsx_sort_nth* selects whenever n >= 2 and 1 <= distinct ranks <= 64; =2: always the sort route
 	unsigned topk_force = 0;         // RSX_TOPK_FORCE=1: rsx_sort_topk* selects whenever n >= 2 and 0 < k <= n; =2: always the sort route
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
@@ -159,6 +162,7 @@ struct Env {
 		nth_force = one_or_two("RSX_NTH_FORCE");
 		within("RSX_LEX_PACK_BYTES", &lex_pack_bytes, 1, 8);
 		number("RSX_UNIQUE_MAX_BITS", &unique_max_bits, 0, (int)UNIQUE_MAX_BITS_COMPILED);
+		number("RSX_GROUP_MAX_BITS", &group_max_bits, 0, (int)GROUP_MAX_BITS_COMPILED);
 		within("RSX_TWO_LEVEL_MIN_LOG2", &two_level_min_log2, 22, 30);
 	}
 };
