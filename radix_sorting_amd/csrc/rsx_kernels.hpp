@@ -1243,6 +1243,12 @@ template <typename KT> __device__ __forceinline__ KT kdf_invert(KT y, const KdfA
 	const KT nsign = (KT)~(KT)((ST)y >> (sizeof(KT) * 8 - 1));   // all ones iff the top bit of the derived key is clear
 	return (KT)(y ^ ((nsign & a.fmask) | a.sflip));
 }
+// kdf_invert(upper | low) from uinv = kdf_invert(upper), one xor per key.  Precondition: `low` has no bit in common with `upper`,
+// and the top bit belongs to `upper`.  kdf_invert xors its argument with a mask that depends on the argument's top bit only;
+// upper | low has upper's top bit, so the mask is upper's, and upper | low == upper ^ low.  That holds in a leaf of a two-level
+// sort: `upper` is what all keys of the leaf share -- the slot's two MSB digits and everything above them, the top bit among
+// them -- and `low` is a key's bits below the lower digit (fewer than sh2 <= 16 of them).
+template <typename KT> __device__ __forceinline__ KT kdf_invert_below(KT uinv, KT low) { return (KT)(uinv ^ low); }
 
 template <typename KT>
 __global__ __launch_bounds__(256) void rsx_fill_runs_kernel(KT *__restrict__ out, u64 n, const u64 *__restrict__ ghist,

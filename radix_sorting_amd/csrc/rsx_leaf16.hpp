@@ -233,23 +233,32 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leaf16_kernel(KT *__rest
 				if (wave_has(j))
 					*(u32x4 *)&stage[8 * (tid + BLOCK * j)] = kv[j];
 		} else {
-			// a value's cell: byte address of its word and the shift of its half; values that do not exist count in the lane's own word
-			auto cell_of = [&](u32 w, int k, bool valid, u32 &sh) -> u32 * {
-				// k even: the value is w[15:0], k odd: w[31:16]; its bin: nb bits from bit D of the value on (one bit-field extract)
-				const u32 o = D + 16u * (u32)(k & 1);   // (uniform)
-				sh = __builtin_amdgcn_ubfe(w, o, 1u) << 4;
-				return &cell[valid ? __builtin_amdgcn_ubfe(w, o + 1u, nb - 1u) : NCELLW + lane];
+			// a value's cell: the word (cell_word) and the half of it (cell_half: 0 or 1); k even: the value is w[15:0], k odd: w[31:16];
+			// its bin: nb bits from bit D of the value on (one bit-field extract each)
+			auto cell_half = [&](u32 w, int k) { return __builtin_amdgcn_ubfe(w, D + 16u * (u32)(k & 1), 1u); };
+			auto cell_word = [&](u32 w, int k) { return __builtin_amdgcn_ubfe(w, D + 16u * (u32)(k & 1) + 1u, nb - 1u); };
+			// Only the vectors that straddle the front's or the back's end hold values that do not exist (they count in the lane's
+			// own word behind the cells and are staged in a place of the lane's own): a wave whose 64 vectors lie wholly inside the
+			// front -- sixty-four vectors never fit into the back -- counts and places without asking (ALL)
+			static_assert(64 * 8 > LEAF16_BACK, "");
+			auto wave_whole = [&](int j) { return 64 * swid + BLOCK * (u32)j + 64u <= front >> 3; };
+			auto count = [&](const u32x4 &x, int nv, auto all_c) {
+				constexpr bool ALL = decltype(all_c)::value;
+#pragma unroll
+				for (int k = 0; k < 8; ++k) {
+					const u32 w = x[k >> 1], cw = cell_word(w, k);
+					__hip_atomic_fetch_add(&cell[ALL || k < nv ? cw : NCELLW + lane], 1u + cell_half(w, k) * 0xFFFFu, __ATOMIC_RELAXED,
+					                       __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
 			};
 			// ---- count
 #pragma unroll
 			for (int j = 0; j < NV; ++j) {
 				if (wave_has(j)) {
-#pragma unroll
-					for (int k = 0; k < 8; ++k) {
-						u32 sh;
-						u32 *a = cell_of(kv[j][k >> 1], k, k < nvalid[j], sh);
-						__hip_atomic_fetch_add(a, 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-					}
+					if (wave_whole(j))
+						count(kv[j], nvalid[j], std::true_type{});
+					else
+						count(kv[j], nvalid[j], std::false_type{});
 				}
 			}
 			__syncthreads();
@@ -332,20 +341,32 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leaf16_kernel(KT *__rest
 				}
 			}
 			__syncthreads();
-			// ---- place: the returning atomic on the bin's start is the key's place (any order inside a bin)
+			// ---- place: the returning atomic on the bin's start is the key's place (any order inside a bin).  A vector's eight
+			// atomics go out together, then its eight stores (rsx_pass16a_kernel's stage_keys): one wait for the LDS per vector, not
+			// one per key
+			auto place = [&](const u32x4 &x, int nv, auto all_c) {
+				constexpr bool ALL = decltype(all_c)::value;
+				u32 old[8];
+#pragma unroll
+				for (int k = 0; k < 8; ++k) {
+					const u32 w = x[k >> 1], cw = cell_word(w, k);
+					old[k] = __hip_atomic_fetch_add(&cell[ALL || k < nv ? cw : NCELLW + lane], 1u + cell_half(w, k) * 0xFFFFu,
+					                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+				}
+#pragma unroll
+				for (int k = 0; k < 8; ++k) {
+					const u32 w = x[k >> 1];
+					const u32 pos = __builtin_amdgcn_ubfe(old[k], cell_half(w, k) << 4, 16u);
+					stage[ALL || k < nv ? pos : CAP + 32 + lane] = (uint16_t)((k & 1) ? (w >> 16) : w);
+				}
+			};
 #pragma unroll
 			for (int j = 0; j < NV; ++j) {
 				if (wave_has(j)) {
-#pragma unroll
-					for (int k = 0; k < 8; ++k) {
-						const u32 w = kv[j][k >> 1];
-						const bool valid = k < nvalid[j];
-						u32 sh;
-						u32 *a = cell_of(w, k, valid, sh);
-						const u32 old = __hip_atomic_fetch_add(a, 1u << sh, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-						const u32 pos = (old >> sh) & 0xFFFFu;
-						stage[valid ? pos : CAP + 32 + lane] = (uint16_t)((k & 1) ? (w >> 16) : w);
-					}
+					if (wave_whole(j))
+						place(kv[j], nvalid[j], std::true_type{});
+					else
+						place(kv[j], nvalid[j], std::false_type{});
 				}
 			}
 		}
@@ -382,17 +403,20 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leaf16_kernel(KT *__rest
 				__syncthreads();
 			}
 		}
-		// ---- write out: four values (8 bytes of LDS) -> four keys (16 bytes) per lane and step
+		// ---- write out: four values (8 bytes of LDS) -> four keys (16 bytes) per lane and step.  Every key of the leaf has the
+		// slot's digits and what lies above them in common, the top bit among them: their share of kdf_invert is done once
+		// (kdf_invert_below)
 		if constexpr (!(C::SKIP & 4)) {
 			const KT upper = (KT)(above | ((KT)((slot - 1) >> 8) << sh1) | ((KT)((slot - 1) & 255u) << sh2));
+			const KT uinv = kdf_invert(upper, ka);
 			KT *o = out + ls.beg;
 			for (u32 i0 = 4 * tid; i0 < cnt; i0 += 4 * BLOCK) {
 				const uint2 x = *(const uint2 *)&stage[i0];
 				KT kk[4];
-				kk[0] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 0u, sh2)), ka);
-				kk[1] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 16u, sh2)), ka);
-				kk[2] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 0u, sh2)), ka);
-				kk[3] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 16u, sh2)), ka);
+				kk[0] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 0u, sh2));
+				kk[1] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 16u, sh2));
+				kk[2] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 0u, sh2));
+				kk[3] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 16u, sh2));
 				if (i0 + 4 <= cnt) {
 					store_chunk<KT, 4>(o + i0, kk);
 				} else {
@@ -603,14 +627,15 @@ __global__ __launch_bounds__(C::BLOCK, 8) void rsx_leaf16w_kernel(KT *__restrict
 		}
 		{
 			const KT upper = (KT)(above | ((KT)((slot - 1) >> 8) << sh1) | ((KT)((slot - 1) & 255u) << sh2));
+			const KT uinv = kdf_invert(upper, ka);   // (the leaf's share of the inversion: kdf_invert_below)
 			KT *o = out + ls.beg;
 			for (u32 i0 = 4 * lane; i0 < cnt; i0 += 4 * 64) {
 				const uint2 x = *(const uint2 *)&stage[i0];
 				KT kk[4];
-				kk[0] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 0u, sh2)), ka);
-				kk[1] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 16u, sh2)), ka);
-				kk[2] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 0u, sh2)), ka);
-				kk[3] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 16u, sh2)), ka);
+				kk[0] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 0u, sh2));
+				kk[1] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 16u, sh2));
+				kk[2] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 0u, sh2));
+				kk[3] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 16u, sh2));
 				if (i0 + 4 <= cnt) {
 					store_chunk<KT, 4>(o + i0, kk);
 				} else {
@@ -794,14 +819,15 @@ __global__ __launch_bounds__(C::BLOCK, 8) void rsx_leaf16q_kernel(KT *__restrict
 		}
 		{
 			const KT upper = (KT)(above | ((KT)((slot - 1) >> 8) << sh1) | ((KT)((slot - 1) & 255u) << sh2));
+			const KT uinv = kdf_invert(upper, ka);   // (the leaf's share of the inversion: kdf_invert_below)
 			KT *o = out + beg;
 			for (u32 i0 = 4 * l16; i0 < cnt; i0 += 4 * 16) {
 				const uint2 x = *(const uint2 *)&stage[i0];
 				KT kk[4];
-				kk[0] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 0u, sh2)), ka);
-				kk[1] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.x, 16u, sh2)), ka);
-				kk[2] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 0u, sh2)), ka);
-				kk[3] = kdf_invert((KT)(upper | __builtin_amdgcn_ubfe(x.y, 16u, sh2)), ka);
+				kk[0] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 0u, sh2));
+				kk[1] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.x, 16u, sh2));
+				kk[2] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 0u, sh2));
+				kk[3] = kdf_invert_below(uinv, (KT)__builtin_amdgcn_ubfe(x.y, 16u, sh2));
 				if (i0 + 4 <= cnt) {
 					store_chunk<KT, 4>(o + i0, kk);
 				} else {

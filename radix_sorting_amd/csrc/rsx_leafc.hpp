@@ -225,7 +225,7 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leafc_kernel(KT *__restr
 		__syncthreads();
 		// ---- write out.  A place's value is the largest mark at or before it.  Wave `wid` takes the blocks of 256 places
 		// wid + NW i, four places per lane: first the running maximum inside every block (kept in registers) and the block's
-		// largest mark, then -- all blocks' maxima are known -- the keys: the upper half from the slot's digits, kdf_invert,
+		// largest mark, then -- all blocks' maxima are known -- the keys: the upper half from the slot's digits, kdf_invert (once per leaf),
 		// 16-byte stores
 		{
 			constexpr int NBI = C::NBI;
@@ -260,6 +260,7 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leafc_kernel(KT *__restr
 				}
 			}
 			const KT upper = (KT)(above | ((KT)((slot - 1) >> 8) << sh1) | ((KT)((slot - 1) & 255u) << sh2));
+			const KT uinv = kdf_invert(upper, ka);   // (the leaf's share of the inversion; a mark is a value of the leaf: below bit sh2)
 			KT *o = out + ls.beg;
 #pragma unroll
 			for (int i = 0; i < NBI; ++i) {
@@ -285,7 +286,7 @@ __global__ __launch_bounds__(C::BLOCK, C::WPE) void rsx_leafc_kernel(KT *__restr
 					KT kk[4];
 #pragma unroll
 					for (int e = 0; e < 4; ++e)
-						kk[e] = kdf_invert((KT)(upper | (KT)m[e]), ka);
+						kk[e] = kdf_invert_below(uinv, (KT)m[e]);
 					if (i0 + 4 <= cnt) {
 						store_chunk<KT, 4>(o + i0, kk);
 					} else {
