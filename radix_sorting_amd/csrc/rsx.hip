@@ -40,8 +40,11 @@
 
 using namespace rsx;
 
-#include "rsx_env.hpp"   // the RSX_* switches
-#include "rsx_ctx.hpp"   // the error convention, DevBuf, Ctx, profiling, get_ctx
+#include "rsx_env.hpp"          // the RSX_* switches
+#include "rsx_seg_layout.hpp"   // SegLayout, SlotParts: where the segmented routes' control block and level-1 slots lie
+#include "rsx_ctx.hpp"          // the error convention, DevBuf, Ctx, profiling, get_ctx
+#include "rsx_route_levels.hpp" // MSB passes and leaves behind a histogram: the control block, the leaves, one and two levels
+#include "rsx_route_blind.hpp"  // ... and without one: gates, sizes, blind_enqueue / pairs_blind_enqueue and their blocking sorts
 
 namespace {
 
@@ -172,6 +175,18 @@ int plan_wait(Ctx &c, Plan *out)
 {
 	HIP_TRY(hipEventSynchronize(c.plan_ev));
 	*out = *c.host_plan;
+	return RSX_OK;
+}
+
+// the exit of the blocking drivers on sorted input (radix_sort.hpp:60-62): no column was sorted by, the result is where the input is
+inline int finish_sorted(rsx_info *info, void **result = nullptr, void *where = nullptr)
+{
+	if (info) {
+		info->early_exit = 2;
+		info->ncols = 0;
+	}
+	if (result)
+		*result = where;
 	return RSX_OK;
 }
 
@@ -402,1102 +417,6 @@ int scatter_pass_to(Ctx &c, const KT *kin, void *kout, u32 out_bytes, const VT *
 	return fail(RSX_EINVAL, "scatter_pass_to: %u-byte keys out of %zu-byte keys", out_bytes, sizeof(KT));
 }
 
-// ---- one MSB pass and leaves (rsx_hybrid.hpp; README.md:647-650) ---------------------------------------------------------
-template <typename KT> struct LeafShapes {
-	typedef LeafCfg<KT, 4, 32, sizeof(KT) == 8 ? 2 : 4, true, false> Small;   // 8 Ki keys: several workgroups per CU
-	typedef LeafCfg<KT, 16, sizeof(KT) == 8 ? 16 : 32> Big;      // as many keys as the LDS stages at once: one workgroup per CU
-	// 4-byte keys: a shape in between (16 Ki keys, two workgroups per CU) -- leaves of 8-16 Ki keys (2^29 keys in 65536 buckets)
-	// in the large shape were no faster than four passes.  8-byte keys: the small shape already holds 64 KiB.
-	static constexpr bool HAS_MEDIUM = sizeof(KT) == 4;
-	typedef LeafCfg<KT, 8, 32, 4, true, false> Medium;
-	// 4-byte keys, leaves read from slots of at most 5120 keys (2^28 keys in 65536 slots: BASELINE.json's headline): the small
-	// shape cut to that size -- twenty rounds per lane instead of thirty-two, 24.5 instead of 37 KiB of LDS: the leaves of 2^28
-	// keys take 0.587 instead of 0.640 ms (tools/ubench/leaf_probe, profiles/r03/leaf_probe.txt; with room for a fifth
-	// workgroup's registers the compiler spills: 1.5 ms)
-	static constexpr bool HAS_FIT = sizeof(KT) == 4;
-	typedef LeafCfg<KT, 4, 20, 4, true, false> Fit;
-	// ... and two smaller cuts for smaller arrays (the slots of 56 Mi .. 100 Mi keys hold up to 2048 keys, those of up to
-	// 157 Mi up to 3072): eight / twelve rounds per lane.  tools/ubench/leaf_probe, 65536 leaves of 1024 keys: 0.229 against
-	// 0.346 ms in the 5120-key shape; of 2048 keys: 0.321 against 0.421
-	typedef LeafCfg<KT, 4, 8, 8, true, false> Fit2k;
-	typedef LeafCfg<KT, 4, 12, 6, true, false> Fit3k;
-	// ... the shape (bits 5, 6, 3: the three cuts) for leaves that lie in slots of `cap` keys
-	static u32 shape_for_slots(u32 cap)
-	{
-		if (HAS_FIT && cap <= (u32)Fit2k::CAP)
-			return 32u;
-		if (HAS_FIT && cap <= (u32)Fit3k::CAP)
-			return 64u;
-		if (HAS_FIT && cap <= (u32)Fit::CAP)
-			return 8u;
-		return shape_for(cap);
-	}
-	// the shape (bit 0 small, bit 2 medium, bit 1 large) for leaves of up to `m` keys
-	static u32 shape_for(u32 m)
-	{
-		if (m <= (u32)Small::CAP)
-			return 1u;
-		if (HAS_MEDIUM && m <= (u32)Medium::CAP)
-			return 4u;
-		return 2u;
-	}
-};
-
-// RSX_NO_HYBRID=1: one pass per kept column whatever the keys look like (the reference's loop, radix_sort.hpp:82-90)
-bool hybrid_enabled() { return !env().no_hybrid; }
-
-template <typename KT> HybCaps hybrid_caps(size_t n)
-{
-	HybCaps caps{0, 0, 0, 0};
-	if constexpr (sizeof(KT) >= 4) {
-		if (hybrid_enabled() && n < ((size_t)1 << 30)) {
-			caps.cap1 = (u32)LeafShapes<KT>::Big::CAP;
-			caps.min_cols1 = 3;
-			// Two levels pay from about 2^27 keys on (tools/size_sweep.py, profiles/r03/size_sweep.txt: 128 Mi keys 1.16 ms
-			// against 1.22 with one pass per column, 256 Mi 1.89 against 2.30; at 64 Mi 0.73 against 0.62 -- a dozen launches
-			// and two host round trips are a fixed cost).  Between the reach of one level (about 7 Mi evenly spread keys)
-			// and that, one pass per kept column.
-			if (n >= ((size_t)1 << env().two_level_min_log2)) {
-				caps.cap2 = (u32)LeafShapes<KT>::Big::CAP;   // (leaves beyond the small shape's 8 Ki keys take the large one)
-				caps.min_cols2 = 4;
-			}
-		}
-	}
-	return caps;
-}
-
-// The capacity of a slot for buckets of `mean` keys: 1.25 times the mean, and at least seven standard deviations of an evenly
-// spread array's bucket sizes above it, rounded up to 256 keys.  (The second term is what small slots need: with 1.25 x alone a
-// mean of 200 keys gets 256-key slots, 3.6 sigma -- evenly spread arrays of 11.5 .. 13 Mi keys overflowed one of their 65536
-// slots in one sort out of seven to nine out of ten and were sorted by one pass per column after a lost attempt.)
-static inline u32 slot_cap_for(u32 mean)
-{
-	u32 r = 0;
-	while ((u64)(r + 1) * (r + 1) <= mean)
-		++r;
-	const u32 need = std::max(mean + mean / 4, mean + 7 * (r + 1) + 8);
-	return ((need + 255) / 256) * 256;
-}
-
-// The capacity -- and the spacing -- of the 256 level-1 slots of a keys-only sort without a histogram.
-// The slots fill at the same rate, so the 256 write streams of the level-1 pass stand at the same offset of their slots at any
-// time, one slot stride apart: with strides of 15 or 17 x 2 MiB (1.5 x 2^30 four-byte keys: 30 MiB) they meet in the same memory
-// channels and the pass runs at 3.6 TB/s instead of 4.5 (tools/stride_probe.py, profiles/r06/stride_probe.txt: +64 KiB .. +1 MiB
-// per slot restore it, +4 MiB = 17 x 2 MiB is as bad again).  Slots of a MiB and more are an ODD number of 64 KiB apart
-// (RSX_NO_ODD_STRIDE=1: as round 5).  RSX_CAP1_PAD_KIB: that many KiB more per slot (the probe).
-template <typename KT> u32 level1_slot_cap(u32 mean)
-{
-	u32 cap1 = slot_cap_for(mean) + env().cap1_pad_kib * (1024u / (u32)sizeof(KT));
-	if (!env().no_odd_stride && (size_t)cap1 * sizeof(KT) >= ((size_t)1 << 20)) {
-		const u32 unit = 65536u / (u32)sizeof(KT);
-		cap1 = (cap1 + unit - 1) / unit * unit;
-		if ((cap1 / unit) % 2u == 0)
-			cap1 += unit;
-	}
-	return cap1;
-}
-
-// 8-byte keys: may the sample choose four-byte level-2 slots (SegCtl::narrow)?  Where rsx_leafk_kernel sorts the slots, from
-// slots of 512 keys (arrays of ~13 Mi keys) on: the second form of the level-2 pass and of the leaves are two more launches, which
-// 8 Mi keys notice (0.267 against 0.252 ms; 16 Mi: 0.328 against 0.337, 64 Mi 0.77 against 0.87, 192 Mi 2.06 against 2.29:
-// tools/u64_threshold_probe.py, keys & 0xFFFFFFFFFF).
-template <typename KT> bool narrow_slots_ok(u32 cap2)
-{
-	return sizeof(KT) == 8 && cap2 >= 512u && cap2 <= 5120u && !env().no_leaf16 && !env().no_narrow_slots;
-}
-
-// Sorts without a histogram of 4-byte keys (all four columns kept): the level-2 pass writes only the low two bytes of the
-// derived keys into its slots and the leaves put the rest back from the slot's digits (RSX_NO_DENSE_SLOTS=1: whole keys).
-// (where the slots fit the leaf shape that reads them: up to 5120 keys each, 2^28 keys in all)
-// the largest two-byte slot there are leaves for: rsx_leaf16_kernel's 5120 values; round 5: 40960 (slots of 2^31 keys) with the
-// counting leaves of rsx_leafc.hpp behind larger shapes of that kernel
-constexpr u32 LEAFC_CAP = 40960;
-template <typename KT> u32 dense_cap_max()
-{
-	if (sizeof(KT) != 4)
-		return 0u;
-	const bool big = !env().no_leafc && !env().no_leaf16 && !env().no_pass16 && !env().no_pass16a && !env().no_unstable;
-	return big ? LEAFC_CAP : (u32)LeafShapes<KT>::Fit::CAP;
-}
-template <typename KT> bool dense_slots(const Ctx &c)
-{
-	if (sizeof(KT) != 4 || env().no_dense_slots || c.slack_cap == 0 || c.slack_cap > dense_cap_max<KT>())
-		return false;
-	if (c.slack_cap > (u32)LeafShapes<KT>::Fit::CAP)
-		return true;   // (rsx_leafc.hpp: on unless dense_cap_max says otherwise)
-	// round 4: rsx_leaf16_kernel (rsx_leaf16.hpp) sorts two-byte slots of every size up to 5120 values faster than the
-	// leaves of whole keys are sorted (tools/ubench/leaf16_probe: 2^28 keys 0.39 against 0.67 ms, 2^27 0.25 against 0.46)
-	if (!env().no_leaf16)
-		return true;
-	// RSX_NO_LEAF16=1, round 3's leaves: slots of 3073 .. 5120 keys only (with the smaller cuts the two-byte leaves are level
-	// or a little behind -- 64 Mi keys 0.565 against 0.548 ms, 128 Mi 0.867 against 0.862); RSX_DENSE_SLOTS=1: every size
-	return env().force_dense_slots || c.slack_cap > (u32)LeafShapes<KT>::Fit3k::CAP;
-}
-
-// The leaves of a level (rsx_leaf_sort_kernel).  `shapes`: bit 0 the shape for leaves of up to 8 Ki keys, bit 1 the one that
-// fills the LDS; a launched shape does nothing unless the device-side plan has leaves of its size, so both may be enqueued
-// before the host knows (nothing then waits for the host).
-template <typename KT>
-int launch_leaves(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, u32 level, u32 shapes, const u64 *off1 = nullptr)
-{
-	typedef typename LeafShapes<KT>::Small S;
-	typedef typename LeafShapes<KT>::Big B;
-	// one workgroup per bucket at level 1; level 2: a workgroup per table entry (0.569 against 0.585 ms for 2^28 keys with
-	// 8192 persistent ones, tools/ubench/leaf_probe; RSX_LEAF_GRID to probe other grids)
-	const unsigned grid_s = level == HYB_TWO_LEVEL ? env().leaf_grid : 256u;
-	const unsigned grid_1 = 65536u;   // the kernels of rsx_leaf16.hpp take one leaf per workgroup (wave, row): the grid IS the table (LEAF_ONE_PER_GROUP)
-	const unsigned grid_b = 256u;
-	const LeafSeg *segtab = level == HYB_TWO_LEVEL ? (const LeafSeg *)((char *)c.seg.p + c.seg_segtab_off) : nullptr;
-	const SegCtl *ctl = (const SegCtl *)c.seg.p;
-	const bool dense = (shapes & 0x100u) != 0;   // (bit 8: the leaves read two-byte slots, dense_slots)
-	ProfScope prof(2, (u64)n * (dense ? 2 + sizeof(KT) : 2 * sizeof(KT)), c.stream);
-	const KT *slots = level == HYB_TWO_LEVEL ? (const KT *)c.slack.p : nullptr;   // (only leaves of a slack attempt name slots)
-	const u32 nopre = env().no_leaf_prefix ? 2u : 0u;   // RSX_NO_LEAF_PREFIX=1: 8-byte-key leaves go through all their columns
-	u32 skip_narrowable = nopre;
-	if constexpr (sizeof(KT) == 8) {
-		if ((shapes & 0x200u) && !env().no_leaf16) {
-			// a sort without a histogram, slots of up to 5120 keys: one placement by twelve bits + register passes on 4- or
-			// 8-byte values (rsx_leafk_kernel, rsx_leaf16.hpp: the instantiation whose carried type the leaves' columns need
-			// works, the other does nothing); what they leave alone goes through the LDS passes of round 3
-			u32 *redo = (u32 *)((char *)c.seg.p + c.seg_redo_off);
-			SegCtl *wctl = (SegCtl *)c.seg.p;
-			// (three shapes by the slots' capacity, as the pairs' leaves: a leaf's fixed costs follow its shape)
-#define RSX_LEAFK(K4, K8)                                                                                                      \
-	do {                                                                                                                       \
-		hipLaunchKernelGGL((rsx_leafk_kernel<KT, u32, K4>), dim3(grid_1), dim3(K4::BLOCK), 0, c.stream, src, aux,               \
-		                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)K4::CAP, slots, c.slack_cap, redo,               \
-		                   (u32)env().leaf16_maxbin);                                                                          \
-		hipLaunchKernelGGL((rsx_leafk_kernel<KT, u64, K8>), dim3(grid_1), dim3(K8::BLOCK), 0, c.stream, src, aux,               \
-		                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)K8::CAP, slots, c.slack_cap, redo,               \
-		                   (u32)env().leaf16_maxbin);                                                                          \
-		if (narrow_slots_ok<KT>(c.slack_cap))   /* four-byte slots (SegCtl::narrow) */                                          \
-			hipLaunchKernelGGL((rsx_leafk_kernel<KT, u32, K4, true>), dim3(grid_1), dim3(K4::BLOCK), 0, c.stream, src, aux,     \
-			                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)K4::CAP, slots, c.slack_cap, redo,           \
-			                   (u32)env().leaf16_maxbin);                                                                      \
-	} while (0)
-			typedef LeafKCfg<512, 5120, 8> K4;
-			typedef LeafKCfg<512, 5120, 8> K8;   // (8-byte values staged in 6 bytes: four workgroups per CU)
-			typedef LeafKCfg<256, 2560, 8, 11> K2;
-			typedef LeafKCfg<128, 1280, 6, 10> K1;
-			typedef LeafKCfg<64, 256, 8, 9> K0;    // slots of up to 256 keys (arrays of up to ~13 Mi keys): a wave per leaf
-			typedef LeafKCfg<64, 512, 8, 10> K0b;  // ... and of 512 (arrays of 11.5 .. 27 Mi keys)
-			if (c.slack_cap <= (u32)K0::CAP && !env().no_leaf16q)
-				RSX_LEAFK(K0, K0);
-			else if (c.slack_cap <= (u32)K0b::CAP && !env().no_leaf16q)
-				RSX_LEAFK(K0b, K0b);
-			else if (c.slack_cap <= (u32)K1::CAP)
-				RSX_LEAFK(K1, K1);
-			else if (c.slack_cap <= (u32)K2::CAP)
-				RSX_LEAFK(K2, K2);
-			else {
-				// the 5120-key shape (arrays above 2^27 keys: BASELINE.json's cfg 3): the 8-byte-carried leaves by their own kernel
-				hipLaunchKernelGGL((rsx_leafk_kernel<KT, u32, K4>), dim3(grid_1), dim3(K4::BLOCK), 0, c.stream, src, aux,
-				                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)K4::CAP, slots, c.slack_cap, redo,
-				                   (u32)env().leaf16_maxbin);
-				hipLaunchKernelGGL((rsx_leafk8_kernel<KT, u64, LeafK8Cfg>), dim3(grid_1), dim3(LeafK8Cfg::BLOCK), 0, c.stream, src, aux,
-				                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)LeafK8Cfg::CAP, slots, c.slack_cap, redo,
-				                   (u32)env().leaf16_maxbin);
-				if (narrow_slots_ok<KT>(c.slack_cap))
-					hipLaunchKernelGGL((rsx_leafk_kernel<KT, u32, K4, true>), dim3(grid_1), dim3(K4::BLOCK), 0, c.stream, src, aux,
-					                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)K4::CAP, slots, c.slack_cap, redo,
-					                   (u32)env().leaf16_maxbin);
-			}
-#undef RSX_LEAFK
-			typedef LeafCfg<u32, 4, 32, 3, true, false> N;
-			hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, N, u32>), dim3(2048), dim3(N::BLOCK), 0, c.stream, src, aux, (u64)n,
-			                   (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, (u32)S::CAP, slots,
-			                   c.slack_cap, nopre, off1, (const u32 *)redo);
-			hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, S>), dim3(2048), dim3(S::BLOCK), 0, c.stream, src, aux, (u64)n,
-			                   (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, (u32)S::CAP, slots,
-			                   c.slack_cap, nopre | 1u, off1, (const u32 *)redo);
-			HIP_TRY(hipGetLastError());
-			return RSX_OK;
-		}
-		// 8-byte keys: leaves whose columns all lie in the low four bytes are carried as 4-byte values (rsx_hybrid.hpp, CT)
-		if (shapes & 1u) {
-			typedef LeafCfg<u32, 4, 32, 3, true, false> N;   // (131 registers: three workgroups per CU)
-			static_assert(N::CAP == S::CAP, "the narrow shape takes the small shape's leaves");
-			hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, N, u32>), dim3(grid_s), dim3(N::BLOCK), 0, c.stream, src, aux, (u64)n,
-			                   (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, (u32)S::CAP, slots,
-			                   c.slack_cap, nopre, off1);
-			skip_narrowable |= 1u;
-		}
-	}
-	if constexpr (sizeof(KT) == 4) {
-		if (dense && !env().no_leaf16) {
-			// two-byte slots: one placement by the top bits + two register passes (rsx_leaf16.hpp); what that kernel leaves
-			// alone (a list; or everything, if the sample saw the low sixteen bits cluster) goes through the two LDS passes
-			u32 *redo = (u32 *)((char *)c.seg.p + c.seg_redo_off);
-			SegCtl *wctl = (SegCtl *)c.seg.p;
-			if (c.slack_cap > 5120u || (env().force_leafc && c.slack_cap <= LEAFC_CAP)) {
-				const unsigned force = env().force_leafc;
-				// round 5, arrays beyond 2^28 keys (rsx_leafc.hpp).  Slots of up to 20480 values (2^30 keys): rsx_leaf16_kernel in a larger
-				// shape -- 13 or 14 bits name a value's bin, 512 or 1024 threads to a leaf --, and behind it the counting leaves for what
-				// it leaves alone; larger slots (2^31 keys: 32 Ki values each): the counting leaves at once.  tools/ubench/leafc_probe,
-				// profiles/r05/leafc_probe.txt: 2^29 keys 0.81 ms against 1.78 counting, 2^30 1.80 against 2.35, 2^31 4.33 against 3.20.
-				// (the shapes' ladder: tools/ubench/leafc_probe at 300 M, 400 M, 2^29, 700 M, 2^30 and 1.5 x 2^30 keys,
-				// profiles/r05/leafc_probe_between.txt -- every step is 10-20 % over the next larger shape at its size)
-				typedef Leaf16Cfg<256, 6144, 8, 12> L6k;
-				typedef Leaf16Cfg<256, 7680, 8, 12> L7k;
-				typedef Leaf16Cfg<512, 10240, 8, 13> L10k;
-				typedef Leaf16Cfg<512, 15360, 8, 13> L15k;
-				typedef Leaf16Cfg<1024, 20480, 8, 14> L20k;
-				const unsigned grid_c = 256u;   // (a workgroup per CU: the cells fill the LDS)
-#define RSX_LAUNCH_LC(NVEC, REDO)                                                                                           \
-				hipLaunchKernelGGL((rsx_leafc_kernel<KT, LeafCCfg<NVEC>>), dim3(grid_c), dim3(LeafCCfg<NVEC>::BLOCK), 0, c.stream, src, aux, \
-				                   (const Plan *)c.plan(), segtab, ctl, ka, 0u, (u32)LeafCCfg<NVEC>::CAP, (const uint16_t *)slots,     \
-				                   c.slack_cap, (const u32 *)(REDO))
-#define RSX_LAUNCH_L16B(CFG, NVEC)                                                                                          \
-				do {                                                                                                        \
-					hipLaunchKernelGGL((rsx_leaf16_kernel<KT, CFG>), dim3(grid_1), dim3(CFG::BLOCK), 0, c.stream, src, aux,   \
-					                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)CFG::CAP, (const uint16_t *)slots,   \
-					                   c.slack_cap, redo, (u32)env().leaf16_maxbin);                                          \
-					RSX_LAUNCH_LC(NVEC, redo);                                                                                \
-				} while (0)
-				const u32 cap = c.slack_cap;
-				// (RSX_FORCE_LEAFC, tests: 1 counting, 2 / 3 / 4 / 5 / 6 the 10240- / 20480- / 6144- / 7680- / 15360-value shape)
-				const unsigned pick = force ? force
-				                            : cap <= (u32)L6k::CAP ? 4u : cap <= (u32)L7k::CAP ? 5u : cap <= (u32)L10k::CAP ? 2u
-				                            : cap <= (u32)L15k::CAP ? 6u : cap <= (u32)L20k::CAP ? 3u : 1u;
-				if (pick == 4 && cap <= (u32)L6k::CAP)
-					RSX_LAUNCH_L16B(L6k, 2);
-				else if (pick == 5 && cap <= (u32)L7k::CAP)
-					RSX_LAUNCH_L16B(L7k, 2);
-				else if (pick == 2 && cap <= (u32)L10k::CAP)
-					RSX_LAUNCH_L16B(L10k, 2);
-				else if (pick == 6 && cap <= (u32)L15k::CAP)
-					RSX_LAUNCH_L16B(L15k, 2);
-				else if (pick == 3 && cap <= (u32)L20k::CAP)
-					RSX_LAUNCH_L16B(L20k, 3);
-				else if (cap <= (u32)LeafCCfg<4>::CAP)
-					RSX_LAUNCH_LC(4, nullptr);
-				else
-					RSX_LAUNCH_LC(5, nullptr);
-#undef RSX_LAUNCH_L16B
-#undef RSX_LAUNCH_LC
-				HIP_TRY(hipGetLastError());
-				return RSX_OK;
-			}
-			typedef Leaf16Cfg<256, 5120, 8, 12> L5k;
-			// (128 threads per leaf for slots of up to 2560 values -- arrays of 52 Mi .. 128 Mi keys: a 1280-value leaf keeps 80 lanes
-			// busy in the register passes, and sixteen small workgroups per CU overlap better than eight: tools/ubench/leaf16_probe,
-			// profiles/r05/leaf16_probe_mid.txt: 56 Mi keys 0.118 against 0.163 ms, 128 Mi 0.214 against 0.252)
-			typedef Leaf16Cfg<128, 2560, 8, 11> L2k;
-			typedef Leaf16WCfg<1024, 10, 4> W1k;   // small slots (arrays of up to ~50 Mi keys): a wave per leaf
-			typedef Leaf16WCfg<512, 9, 4> W512;
-			// ... and, round 5, up to 2048 values (arrays of up to ~100 Mi keys: two chunks of sixteen values per lane in the register
-			// passes, slots read from both ends behind rsx_pass16a_kernel): tools/ubench/leaf16_probe against the 128-thread
-			// workgroup shape -- 54 Mi keys 0.110 against 0.119 ms, 64 Mi 0.131 / 0.143, 80 Mi 0.145 / 0.167, 96 Mi 0.162 / 0.180
-			typedef Leaf16WCfg<2048, 10, 4> W2k;
-			if (c.slack_cap > (u32)W1k::CAP && c.slack_cap <= (u32)W2k::CAP && !env().no_leaf16w2k) {
-				hipLaunchKernelGGL((rsx_leaf16w_kernel<KT, W2k>), dim3(grid_1 / W2k::NW), dim3(W2k::BLOCK), 0, c.stream, src, aux,
-				                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)W2k::CAP, (const uint16_t *)slots, c.slack_cap);
-				HIP_TRY(hipGetLastError());
-				return RSX_OK;
-			}
-			if (c.slack_cap <= (u32)W1k::CAP) {
-				// (no list, no second launch: the wave kernel goes on until its leaf is in order)
-				typedef Leaf16QCfg<4> Q256;            // slots of up to 256 values (arrays of up to ~13 Mi keys): four leaves per wave
-				if (c.slack_cap <= (u32)Q256::CAP && !env().no_leaf16q)
-					hipLaunchKernelGGL((rsx_leaf16q_kernel<KT, Q256>), dim3(grid_1 / Q256::ROWS), dim3(Q256::BLOCK), 0, c.stream, src, aux,
-					                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)Q256::CAP, (const uint16_t *)slots, c.slack_cap);
-				else if (c.slack_cap <= (u32)W512::CAP)
-					hipLaunchKernelGGL((rsx_leaf16w_kernel<KT, W512>), dim3(grid_1 / W512::NW), dim3(W512::BLOCK), 0, c.stream, src, aux,
-					                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)W512::CAP, (const uint16_t *)slots, c.slack_cap);
-				else
-					hipLaunchKernelGGL((rsx_leaf16w_kernel<KT, W1k>), dim3(grid_1 / W1k::NW), dim3(W1k::BLOCK), 0, c.stream, src, aux,
-					                   (const Plan *)c.plan(), segtab, wctl, ka, 0u, (u32)W1k::CAP, (const uint16_t *)slots, c.slack_cap);
-				HIP_TRY(hipGetLastError());
-				return RSX_OK;
-			}
-#define RSX_LAUNCH_L16(KERNEL, CFG, GRID)                                                                                     \
-			hipLaunchKernelGGL((KERNEL<KT, CFG>), dim3(GRID), dim3(CFG::BLOCK), 0, c.stream, src, aux, (const Plan *)c.plan(),  \
-			                   segtab, wctl, ka, 0u, (u32)CFG::CAP, (const uint16_t *)slots, c.slack_cap, redo,                \
-			                   (u32)env().leaf16_maxbin)
-			if (c.slack_cap <= (u32)L2k::CAP)
-				RSX_LAUNCH_L16(rsx_leaf16_kernel, L2k, grid_1);
-			else
-				RSX_LAUNCH_L16(rsx_leaf16_kernel, L5k, grid_1);
-#undef RSX_LAUNCH_L16
-			typedef typename LeafShapes<KT>::Fit F_;
-			hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, F_, uint16_t, true>), dim3(4096), dim3(F_::BLOCK), 0, c.stream, src, aux,
-			                   (u64)n, (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, (u32)F_::CAP, slots,
-			                   c.slack_cap, nopre, off1, (const u32 *)redo);
-			HIP_TRY(hipGetLastError());
-			return RSX_OK;
-		}
-	}
-	if constexpr (LeafShapes<KT>::HAS_FIT) {
-		// the shapes cut to the slots' size (exactly one of them is asked for; each takes the leaves up to its capacity)
-#define RSX_LAUNCH_FIT(BIT, SHAPE)                                                                                          \
-		if (shapes & (BIT)) {                                                                                               \
-			typedef typename LeafShapes<KT>::SHAPE F_;                                                                      \
-			if (dense)                                                                                                      \
-				hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, F_, uint16_t, true>), dim3(grid_s), dim3(F_::BLOCK), 0, c.stream, \
-				                   src, aux, (u64)n, (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, \
-				                   (u32)F_::CAP, slots, c.slack_cap, nopre, off1);                                          \
-			else                                                                                                            \
-				hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, F_>), dim3(grid_s), dim3(F_::BLOCK), 0, c.stream, src, aux,     \
-				                   (u64)n, (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u,       \
-				                   (u32)F_::CAP, slots, c.slack_cap, nopre, off1);                                          \
-		}
-		RSX_LAUNCH_FIT(32u, Fit2k)
-		RSX_LAUNCH_FIT(64u, Fit3k)
-		RSX_LAUNCH_FIT(8u, Fit)
-#undef RSX_LAUNCH_FIT
-	}
-	if (shapes & 1u)
-		hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, S>), dim3(grid_s), dim3(S::BLOCK), 0, c.stream, src, aux, (u64)n,
-		                   (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, 0u, (u32)S::CAP, slots,
-		                   c.slack_cap, skip_narrowable, off1);
-	typedef typename LeafShapes<KT>::Medium M;
-	const u32 big_lo = LeafShapes<KT>::HAS_MEDIUM ? (u32)M::CAP : (u32)S::CAP;
-	if constexpr (LeafShapes<KT>::HAS_MEDIUM) {
-		if (shapes & 4u)
-			hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, M>), dim3(level == HYB_TWO_LEVEL ? env().leaf_grid : 256u), dim3(M::BLOCK), 0, c.stream, src,
-			                   aux, (u64)n, (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, (u32)S::CAP, (u32)M::CAP,
-			                   slots, c.slack_cap, nopre, off1);
-	}
-	if (shapes & 2u)
-		hipLaunchKernelGGL((rsx_leaf_sort_kernel<KT, B>), dim3(grid_b), dim3(B::BLOCK), 0, c.stream, src, aux, (u64)n,
-		                   (const u64 *)c.ghist(), (const Plan *)c.plan(), segtab, ctl, ka, level, big_lo, (u32)B::CAP, slots,
-		                   c.slack_cap, nopre, off1);
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// The level-2 pass of a keys-only sort of 4-byte keys without a histogram writes whole 64-byte atoms (rsx_pass16a_kernel,
-// rsx_pass16.hpp) where the leaves are rsx_leaf16_kernel's (slots of more than 1024 values: arrays from about 52 Mi keys),
-// which read a slot from both ends; its tiles are Pass16aCfg::TILE keys.
-template <typename KT> bool pass16a_wanted(const Ctx &c)
-{
-	if constexpr (sizeof(KT) == 4)
-	{
-		if (!dense_slots<KT>(c) || env().no_pass16 || env().no_pass16a || env().no_unstable || env().no_leaf16)
-			return false;
-		if (c.slack_cap > 1024u)
-			return true;
-		// slots of 1024 values (38 .. 52 M keys; the wave per leaf reads both ends since round 5): where the 128 places kept for a
-		// slot's back still leave its front the room slot_cap_for wanted for the whole slot -- mean + 7 standard deviations:
-		// 37.7 M .. 45.9 M keys (the reference's own headline size, 4 * 10^7, among them)
-		if (c.slack_cap == 1024u && c.slack_mean) {
-			u32 r = 0;
-			while ((u64)(r + 1) * (r + 1) <= c.slack_mean)
-				++r;
-			return c.slack_mean + 7 * (r + 1) + 8 <= c.slack_cap - LEAF16_BACK;
-		}
-		return false;
-	}
-	return false;
-}
-
-// a pass inside the level-1 buckets (SEG instantiation of the pass kernel): j < 0 the one by the level-2 column (runs in
-// SEG_MODE_LEAVES), j >= 0 LSB-first pass j (runs in SEG_MODE_LSD).  aux -> src, src -> aux for odd j.
-// j == -2: the slack attempt (aux -> the slots of c.slack, no counts needed).
-// blind (a sort without a histogram, sort_keys_blind): 1 = its level-1 pass (`aux` = the caller's array -> the 256 slots of
-// c.slack1, by the top column, status region 1), 2 = its level-2 pass (j == -2, reading c.slack1 instead of `aux`).
-// Rows of status words (and tile-table entries) a segmented pass may need beyond n / TILE: a partial tile per level-1 bucket, and
-// -- 8-byte keys, whose level-1 pass may be rsx_pass32a_kernel in front of the CHAINED level-2 pass -- one more per bucket for
-// what lies at its slot's end (rsx_seg_tiles_kernel, back_cap).
-template <typename KT> constexpr u64 seg_extra_rows() { return sizeof(KT) == 8 ? 512 : 256; }
-
-// 8-byte keys, the level-2 pass into FOUR-byte slots (SegCtl::narrow) as rsx_pass64a_kernel: whole atoms, cursors, two-ended slots
-// (rsx_leafk_kernel's SLOT32 form reads both ends whatever its shape)
-template <typename KT> bool pass64a_narrow_wanted(const Ctx &c)
-{
-	if (sizeof(KT) != 8 || !narrow_slots_ok<KT>(c.slack_cap) || env().no_pass64a || env().no_unstable || !c.slack_mean)
-		return false;
-	// the 128 places kept for a slot's back must leave its front mean + 6 standard deviations (what is carried to the back, a
-	// few dozen values per slot, comes on top): just below a step of slot_cap_for they do not -- 64 Mi keys, mean 1024 in slots
-	// of 1280, lost the attempt -- and the chained pass, whose slots have no back, stays
-	u32 r = 0;
-	while ((u64)(r + 1) * (r + 1) <= c.slack_mean)
-		++r;
-	return c.slack_mean + 6 * (r + 1) + 8 <= c.slack_cap - Pass2wCfg<u32>::BACK;
-}
-
-template <typename KT>
-int launch_seg_pass(Ctx &c, const KT *aux, KT *src, size_t n, KdfArgs<KT> ka, int j, int blind = 0)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	const u64 rows = (n + C2::TILE - 1) / C2::TILE + seg_extra_rows<KT>();
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	char *base = (char *)c.seg.p + c.seg_status_off + (size_t)(blind == 1 ? 1 : j < 0 ? 0 : j) * st_bytes;
-	SegArgs sa{};
-	sa.ctl = (const SegCtl *)c.seg.p;
-	sa.hist = (const u32 *)((char *)c.seg.p + c.seg_hist_off);
-	sa.tiles = (const SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-	sa.slots = (u32)sizeof(KT) - 1;
-	sa.slack_cap = blind == 1 ? c.slack1_cap : j == -2 ? c.slack_cap : 0u;
-	sa.overflow = &((SegCtl *)c.seg.p)->overflow;
-	KT *const second = blind == 1 ? src : blind == 2 ? const_cast<KT *>(aux) : nullptr;
-	if (j == -2)
-		src = (KT *)c.slack.p;
-	// blind: `src` (level-1 pass) / `aux` (level-2 pass) name the caller's second buffer when the first slack1_lo level-1 slots
-	// lie there (blind_enqueue); the others lie in c.slack1
-	if (blind == 1 || blind == 2) {
-		KT *first = (KT *)c.slack1.p;
-		if (second && c.slack1_lo) {
-			sa.lo_slots = c.slack1_lo;
-			// (virtual slot 0 of the scratch part: slack1_lo slots before the array)
-			const uintptr_t lo_a = (uintptr_t)second, hi_a = (uintptr_t)c.slack1.p - (size_t)c.slack1_lo * c.slack1_cap * sizeof(KT);
-			if (blind == 1) {
-				// one base for the level-1 pass's stores, the parts' offsets in its run offsets (blind_enqueue has checked
-				// that both lie within 2^32 elements of the lower one)
-				const uintptr_t base_a = std::min(lo_a, hi_a);
-				sa.out_off_lo = (u32)((lo_a - base_a) / sizeof(KT));
-				sa.out_off_hi = (u32)((hi_a - base_a) / sizeof(KT));
-				first = (KT *)base_a;
-			} else {
-				sa.kin_hi = (const void *)hi_a;
-				first = second;
-			}
-		}
-		if (blind == 1)
-			src = first;
-		else
-			aux = first;
-	}
-	const bool dense = sizeof(KT) == 4 && blind == 2 && dense_slots<KT>(c);   // (keys written as two bytes: its own line in the profile)
-	ProfScope prof(dense ? 3 : 1, (u64)n * (dense ? sizeof(KT) + 2 : 2 * sizeof(KT)), c.stream);
-	const bool plain = ka.fmask == 0 && ka.sflip == 0 && ka.desc == 0;
-	u32 flags = j == -2 ? (u32)SCATTER_SEG_SLACK : j < 0 ? (u32)SCATTER_SEG_LEAVES : 0u;
-	if (blind)
-		flags |= SCATTER_BLIND | (blind == 1 ? (u32)SCATTER_BLIND_TOP : 0u);
-	// keys only, and what these two passes write is sorted by leaves that do not care in which order a bucket's keys arrive
-	// (any ascending order of equal bits is the reference's output): no row of cells per wave, no layout over the rows
-	if (blind && !env().no_unstable)
-		flags |= SCATTER_UNSTABLE;
-	const u32 pi = j < 0 ? 0u : (u32)j;
-	const unsigned grid = blind == 1 ? (unsigned)(rows - seg_extra_rows<KT>()) : (unsigned)rows;
-	const u32 shift0 = 0u;   // (every segmented pass reads its column from the device-side plan)
-#define RSX_LAUNCH_SEG(DIGV)                                                                                               \
-	hipLaunchKernelGGL((rsx_scatter2_kernel<KT, NoVal, u32, C2, false, DIGV, false, KT, true>), dim3(grid),                 \
-	                   dim3(C2::BLOCK), 0, c.stream, aux, src, (const NoVal *)nullptr, (NoVal *)nullptr, (u64)n, shift0,     \
-	                   (const u64 *)c.ghist(), 1u, (u32 *)(base + 256), (u32 *)base, ka, flags, (u64 *)nullptr,             \
-	                   (const Plan *)c.plan(), pi, 0u, (const u32 *)nullptr, sa)
-	if constexpr (sizeof(KT) == 4) {
-		if (dense && pass16a_wanted<KT>(c)) {
-			// ... and with whole 64-byte atoms: a workgroup takes a range of tiles and carries what does not fill an atom
-			const unsigned pgrid = 512;
-			if (plain)
-				hipLaunchKernelGGL((rsx_pass16a_kernel<KT, DIG_PLAIN>), dim3(pgrid), dim3(Pass16aCfg::BLOCK), 0, c.stream, (const KT *)aux,
-				                   (const KT *)sa.kin_hi, sa.lo_slots, (unsigned short *)src, sa.tiles, sa.ctl, (const Plan *)c.plan(),
-				                   (u32 *)(base + 256), sa.slack_cap, sa.overflow, ka);
-			else
-				hipLaunchKernelGGL((rsx_pass16a_kernel<KT, DIG_GENERIC>), dim3(pgrid), dim3(Pass16aCfg::BLOCK), 0, c.stream, (const KT *)aux,
-				                   (const KT *)sa.kin_hi, sa.lo_slots, (unsigned short *)src, sa.tiles, sa.ctl, (const Plan *)c.plan(),
-				                   (u32 *)(base + 256), sa.slack_cap, sa.overflow, ka);
-			HIP_TRY(hipGetLastError());
-			return RSX_OK;
-		}
-		if (dense && !env().no_pass16 && !env().no_unstable && !env().no_leaf16) {
-			// round 5: the pass as a kernel of its own (rsx_pass16.hpp): values staged in two bytes, two workgroups per CU, cursors
-			// instead of the chain, 16-byte stores.  (Its slots hold a bucket's values in arbitrary order: for leaves that sort.)
-			const u32 *btile = (const u32 *)((char *)c.seg.p + c.seg_btile_off);
-#define RSX_LAUNCH_P16(DIGV, CFG)                                                                                          \
-	hipLaunchKernelGGL((rsx_pass16_kernel<KT, DIGV, CFG>), dim3(grid), dim3(CFG::BLOCK), 0, c.stream, (const KT *)aux,      \
-	                   (const KT *)sa.kin_hi, sa.lo_slots, (unsigned short *)src, sa.tiles, btile, sa.ctl,                  \
-	                   (const Plan *)c.plan(), (u32 *)(base + 256), sa.slack_cap, sa.overflow, ka, (u32)env().pass16_dbg)
-			if (env().pass16_wgs == 1) {
-				if (plain)
-					RSX_LAUNCH_P16(DIG_PLAIN, Pass16Cfg<1>);
-				else
-					RSX_LAUNCH_P16(DIG_GENERIC, Pass16Cfg<1>);
-			} else {
-				if (plain)
-					RSX_LAUNCH_P16(DIG_PLAIN, Pass16Cfg<2>);
-				else
-					RSX_LAUNCH_P16(DIG_GENERIC, Pass16Cfg<2>);
-			}
-#undef RSX_LAUNCH_P16
-			HIP_TRY(hipGetLastError());
-			return RSX_OK;
-		}
-		if (dense) {
-			// 4-byte keys, every column kept: the leaves sort by the two low bytes and the slot says the rest -- the pass writes
-			// the low half of every DERIVED key (rsx_leaf_sort_kernel, DENSE)
-#define RSX_LAUNCH_SEG16(DIGV)                                                                                             \
-	hipLaunchKernelGGL((rsx_scatter2_kernel<KT, NoVal, u32, C2, false, DIGV, false, uint16_t, true>), dim3(grid),           \
-	                   dim3(C2::BLOCK), 0, c.stream, aux, (uint16_t *)src, (const NoVal *)nullptr, (NoVal *)nullptr, (u64)n, \
-	                   shift0, (const u64 *)c.ghist(), 1u, (u32 *)(base + 256), (u32 *)base, ka, flags, (u64 *)nullptr,      \
-	                   (const Plan *)c.plan(), pi, 0u, (const u32 *)nullptr, sa)
-			if (plain)
-				RSX_LAUNCH_SEG16(DIG_PLAIN);
-			else
-				RSX_LAUNCH_SEG16(DIG_GENERIC);
-#undef RSX_LAUNCH_SEG16
-			HIP_TRY(hipGetLastError());
-			return RSX_OK;
-		}
-	}
-	if (plain)
-		RSX_LAUNCH_SEG(DIG_PLAIN);
-	else
-		RSX_LAUNCH_SEG(DIG_GENERIC);
-#undef RSX_LAUNCH_SEG
-	if constexpr (sizeof(KT) == 8) {
-		if (blind == 2 && narrow_slots_ok<KT>(c.slack_cap)) {
-			// ... and the form that writes the low word of every derived key (SegCtl::narrow decides on the device which of the
-			// two works; it uses its own status words: the same region, which the form that left has not touched)
-#define RSX_LAUNCH_SEG32(DIGV)                                                                                             \
-	hipLaunchKernelGGL((rsx_scatter2_kernel<KT, NoVal, u32, C2, false, DIGV, false, u32, true>), dim3(grid),                \
-	                   dim3(C2::BLOCK), 0, c.stream, aux, (u32 *)src, (const NoVal *)nullptr, (NoVal *)nullptr, (u64)n,     \
-	                   shift0, (const u64 *)c.ghist(), 1u, (u32 *)(base + 256), (u32 *)base, ka, flags, (u64 *)nullptr,     \
-	                   (const Plan *)c.plan(), pi, 0u, (const u32 *)nullptr, sa)
-			if (pass64a_narrow_wanted<KT>(c)) {
-				typedef Pass2wCfg<u32> P64;
-				hipLaunchKernelGGL((rsx_pass64a_kernel<KT, u32>), dim3(P64::GRID), dim3(P64::BLOCK), 0, c.stream, (const KT *)aux,
-				                   (const KT *)sa.kin_hi, sa.lo_slots, (u32 *)src, sa.tiles, sa.ctl, (const Plan *)c.plan(),
-				                   (u32 *)(base + 256), sa.slack_cap, sa.overflow, ka);
-				if (c.narrow1 && second) {
-					// SegCtl::narrow == 2: the level-1 slots are four-byte places in the caller's second buffer (blind_enqueue), the
-					// same element indices; what they hold is derived already
-					typedef Pass64aCfgLow P64L;
-					hipLaunchKernelGGL((rsx_pass64a_kernel<u32, u32, P64L>), dim3(P64L::GRID), dim3(P64L::BLOCK), 0, c.stream, (const u32 *)second,
-					                   (const u32 *)nullptr, 0u, (u32 *)src, sa.tiles, sa.ctl, (const Plan *)c.plan(),
-					                   (u32 *)(base + 256), sa.slack_cap, sa.overflow, KdfArgs<u32>{0, 0, 0});
-				}
-			} else if (plain)
-				RSX_LAUNCH_SEG32(DIG_PLAIN);
-			else
-				RSX_LAUNCH_SEG32(DIG_GENERIC);
-#undef RSX_LAUNCH_SEG32
-		}
-	}
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// where the parts of a two-level sort's device-side state lie in c.seg
-// bytes of c.seg for a two-level sort of n keys (seg_layout below)
-// rows of the tile table of a two-level sort's level-2 pass: the tiles of the pass that may run (the chained pass's, or the smaller
-// ones of rsx_pass16a_kernel / rsx_pass64a_kernel) + per bucket a partial tile and one for what lies at its slot's end
-template <typename KT> u64 seg_tile_rows(size_t n, u64 rows)
-{
-	if (sizeof(KT) == 4)
-		return (n + Pass16aCfg::TILE - 1) / Pass16aCfg::TILE + 514;
-	return std::max<u64>(rows, (n + Pass2wCfg<u32>::TILE - 1) / Pass2wCfg<u32>::TILE + 514);
-}
-
-template <typename KT> size_t seg_bytes(size_t n)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	const u64 rows = (n + C2::TILE - 1) / C2::TILE + seg_extra_rows<KT>();
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	const size_t hist_bytes = (size_t)256 * (sizeof(KT) - 1) * 256 * sizeof(u32);
-	const u64 tile_rows = seg_tile_rows<KT>(n, rows);
-	return 256 + hist_bytes + (sizeof(KT) - 1) * st_bytes + 65536 * sizeof(LeafSeg) + tile_rows * sizeof(SegTile) + 260 * sizeof(u32) +
-	       65536 * sizeof(u32);
-}
-
-template <typename KT> int seg_layout(Ctx &c, size_t n)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	const u64 rows = (n + C2::TILE - 1) / C2::TILE + seg_extra_rows<KT>();
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	const size_t hist_bytes = (size_t)256 * (sizeof(KT) - 1) * 256 * sizeof(u32);
-	c.seg_hist_off = 256;
-	c.seg_status_off = c.seg_hist_off + hist_bytes;
-	c.seg_segtab_off = c.seg_status_off + (sizeof(KT) - 1) * st_bytes;
-	c.seg_tiles_off = c.seg_segtab_off + 65536 * sizeof(LeafSeg);
-	const u64 tile_rows = seg_tile_rows<KT>(n, rows);
-	c.seg_btile_off = c.seg_tiles_off + tile_rows * sizeof(SegTile);
-	c.seg_redo_off = c.seg_btile_off + 260 * sizeof(u32);   // the leaves rsx_leaf16_kernel leaves to rsx_leaf_sort_kernel
-	const void *before = c.seg.p;
-	RSX_TRY(c.seg.ensure(c.seg_redo_off + 65536 * sizeof(u32)));
-	if (c.seg.p != before || c.seg.external)   // (a new control block -- or a caller's workspace, whose contents are scratch: SegCtl::boff_*)
-		HIP_TRY(hipMemsetAsync(c.seg.p, 0, 256, c.stream));
-	return RSX_OK;
-}
-
-// What a sort of n keys WITHOUT a histogram needs on top of that (blind_enqueue): the level-1 slots that do not fit the
-// caller's second buffer, the level-2 slots, the control block / tables / status words of the two passes.
-template <typename KT> void blind_sizes(size_t n, size_t *gscan, size_t *seg, size_t *slack1, size_t *slack)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	const u32 cap1 = level1_slot_cap<KT>((u32)(n >> 8)), cap2 = slot_cap_for((u32)(n >> 16));
-	const u32 lo = cap1 >= (u32)C2::TILE ? (u32)std::min<size_t>(n / cap1, 255) : 0u;
-	const size_t slot2 = (sizeof(KT) == 4 && cap2 <= dense_cap_max<KT>()) ? 2 : sizeof(KT);
-	*gscan = 256 * sizeof(u64);
-	*seg = (seg_bytes<KT>(n) + 255) & ~(size_t)255;
-	*slack1 = ((((size_t)(256 - lo) * cap1 + C2::TILE) * sizeof(KT)) + 255) & ~(size_t)255;
-	*slack = ((((size_t)65536 * cap2 + C2::TILE) * slot2) + 255) & ~(size_t)255;
-}
-
-// ... handed to the context if the workspace has it (rsx_workspace_bytes_fast): the attempt is then made inside the workspace
-template <typename KT> void borrow_blind(Ctx &v, char *p, char *ws_end, size_t n)
-{
-	if constexpr (sizeof(KT) >= 4) {
-		size_t g, sg, s1, s2;
-		blind_sizes<KT>(n, &g, &sg, &s1, &s2);
-		p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-		if (n < ((size_t)1 << 22) || n >= ((size_t)1 << 30) || p + g + sg + s1 + s2 > ws_end)
-			return;
-		v.gscan.borrow(p, g);
-		p += g;
-		v.seg.borrow(p, sg);
-		p += sg;
-		v.slack1.borrow(p, s1);
-		p += s1;
-		v.slack.borrow(p, s2);
-		v.ws_blind = true;
-	}
-}
-
-
-// The second level of a two-level sort.  Pass 1 (by the highest kept column, src -> aux) is on its way; `plan` says so.
-// Ends with the sorted keys in the buffer the reference's parity rule names (radix_sort.hpp:92); *result says which.
-template <typename KT>
-int sort_keys_two_level(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, const Plan &plan, KT **result, u32 *how)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	const u64 rows = (n + C2::TILE - 1) / C2::TILE + seg_extra_rows<KT>();
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	RSX_TRY(seg_layout<KT>(c, n));
-	SegCtl *ctl = (SegCtl *)c.seg.p;
-	u32 *seghist = (u32 *)((char *)c.seg.p + c.seg_hist_off);
-	SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-	LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
-	u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
-	KT *final = (plan.ncols & 1) ? aux : src;
-	if (!c.seg_ev)
-		HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
-	// control block, digit counts and the status words of the first segmented pass, zeroed together
-	HIP_TRY(hipMemsetAsync(c.seg.p, 0, c.seg_status_off + st_bytes, c.stream));
-	hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
-	                   (u32)C2::TILE, tiles, ctl, btile);
-	HIP_TRY(hipGetLastError());
-	// The slack attempt: evenly spread keys need no counts for the second pass.  Every (digit, digit) bucket gets a slot of
-	// 1.25 times its expected size in a scratch array and the pass writes each key where the look-back chain puts it inside
-	// its bucket's slot; the bucket sizes are then read off the chain, and the leaves gather from the slots into the dense
-	// result.  One read of the keys less than the counted path below (rsx_seg_hist1_kernel: 0.25 of 2.1 ms at 2^28 keys).
-	// A slot that overflows (keys clustered after all) only costs the attempt: pass 1's output in `aux` is untouched.
-	c.slack_cap = 0;
-	if (!env().no_slack && n >= ((size_t)1 << 26)) {
-		const u32 mean = (u32)(n >> 16);
-		const u32 cap = slot_cap_for(mean);
-		if (cap <= (u32)LeafShapes<KT>::Big::CAP && c.slack.ensure(((size_t)65536 * cap + C2::TILE) * sizeof(KT)) == RSX_OK) {
-			c.slack_cap = cap;
-			RSX_TRY(launch_seg_pass<KT>(c, aux, src, n, ka, -2));
-			hipLaunchKernelGGL((rsx_seg_slack_plan_kernel<u32>), dim3(256), dim3(256), 0, c.stream,
-			                   (const u32 *)((char *)c.seg.p + c.seg_status_off + 256), (const u32 *)btile, (const u64 *)c.ghist(),
-			                   (const Plan *)c.plan(), ctl, segtab, cap, c.dev_host_segctl);
-			HIP_TRY(hipGetLastError());
-			HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-			RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_TWO_LEVEL, LeafShapes<KT>::shape_for_slots(cap)));
-			HIP_TRY(hipEventSynchronize(c.seg_ev));
-			if (c.host_segctl->mode == SEG_MODE_LEAVES) {
-				*result = final;
-				*how = 4u;
-				return RSX_OK;
-			}
-			// a slot overflowed: the counted path, from `aux` again
-			c.slack_cap = 0;
-			HIP_TRY(hipMemsetAsync(c.seg.p, 0, c.seg_status_off + st_bytes, c.stream));
-			hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n,
-			                   (const Plan *)c.plan(), (u32)C2::TILE, tiles, ctl, btile);
-		} else {
-			(void)hipGetLastError();
-		}
-	}
-	{
-		ProfScope prof(0, (u64)n * sizeof(KT), c.stream);
-		hipLaunchKernelGGL((rsx_seg_hist1_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, (const KT *)aux, (const SegTile *)tiles,
-		                   (const SegCtl *)ctl, (const Plan *)c.plan(), ka, seghist);
-	}
-	hipLaunchKernelGGL((rsx_seg_plan_kernel<KT>), dim3(256), dim3(256), 0, c.stream, seghist, (const u64 *)c.ghist(), (u64)n,
-	                   (const Plan *)c.plan(), ctl, segtab, (u32)LeafShapes<KT>::Big::CAP, c.dev_host_segctl, 0u);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-	// the pass by the level-2 column and the small leaves are enqueued before the host knows whether the (digit, digit)
-	// buckets fit leaves: they do nothing if not
-	RSX_TRY(launch_seg_pass<KT>(c, aux, src, n, ka, -1));
-	RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_TWO_LEVEL, 1u));
-	HIP_TRY(hipEventSynchronize(c.seg_ev));
-	const SegCtl hc = *c.host_segctl;
-	if (hc.mode == SEG_MODE_LEAVES) {
-		if (hc.maxleaf > (u32)LeafShapes<KT>::Small::CAP)   // (rare: the leaves need a larger shape)
-			RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_TWO_LEVEL, LeafShapes<KT>::shape_for(hc.maxleaf)));
-	} else {
-		// keys clustered in their top two columns: one pass per remaining column inside the level-1 buckets, LSB first
-		// (the counts of the columns below the level-2 one are only made now)
-		if (plan.ncols > 2) {
-			ProfScope prof(0, (u64)n * sizeof(KT), c.stream);
-			hipLaunchKernelGGL((rsx_seg_hist_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, (const KT *)aux, (const SegTile *)tiles,
-			                   (const SegCtl *)ctl, (const Plan *)c.plan(), ka, seghist);
-		}
-		hipLaunchKernelGGL((rsx_seg_plan_kernel<KT>), dim3(256), dim3(256), 0, c.stream, seghist, (const u64 *)c.ghist(), (u64)n,
-		                   (const Plan *)c.plan(), ctl, segtab, 0u, (SegCtl *)nullptr, 1u);
-		if (plan.ncols > 2)
-			HIP_TRY(hipMemsetAsync((char *)c.seg.p + c.seg_status_off + st_bytes, 0, (plan.ncols - 2) * st_bytes, c.stream));
-		for (u32 j = 0; j + 1 < plan.ncols; ++j)
-			RSX_TRY(launch_seg_pass<KT>(c, aux, src, n, ka, (int)j));
-	}
-	*result = final;
-	*how = hc.mode == SEG_MODE_LEAVES ? 2u : 3u;
-	return RSX_OK;
-}
-
-// ---- two MSB passes and leaves WITHOUT the histogram (rsx_hybrid.hpp, rsx_blind_precheck_kernel) -----------------------------
-// For the arrays a two-level sort is for (hybrid_caps: cap2), blocking keys-only sorts.  *done = 1: sorted, *result set.
-// *done = 0: called off (the sample did not prove what it has to, or a slot overflowed) -- `src` and `aux` are untouched and
-// the caller runs the ordinary path.  A context that has been called off skips the next attempts of its kind (1, 3, 7 ... 31 sorts).
-template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_, bool counted_too = false);
-// kinds of sorts that learn separately: 0 / 1 keys only (4- / 8-byte keys), 2 rank sorts, 3 key + payload sorts
-template <typename KT> constexpr int blind_kind(size_t payload_bytes, bool rank = false)
-{
-	return payload_bytes ? (rank ? 2 : 3) : (sizeof(KT) == 8 ? 1 : 0);
-}
-inline void blind_called_off(Ctx &c, int kind)
-{
-	c.blind_backoff[kind] = std::min<u32>(2 * c.blind_backoff[kind] + 1, 31);
-	c.blind_skip[kind] = c.blind_backoff[kind];
-}
-// rsx_reload_env() makes every context forget what it has learnt about its inputs (and about its device's memory)
-inline void blind_refresh(Ctx &c)
-{
-	const u32 epoch = g_env_epoch.load();
-	if (c.env_epoch != epoch) {
-		c.env_epoch = epoch;
-		c.blind_no_room = false;
-		for (int k = 0; k < 4; ++k)
-			c.blind_skip[k] = c.blind_backoff[k] = 0;
-		c.log_skip = c.log_backoff = 0;
-		c.boff_forget = true;   // (... and the device-side one of the device-scheduled sorts, SegCtl::boff_*: zeroed by the next attempt)
-	}
-}
-// rsx_reload_env: the context forgets the attempts it lost -- the host's counters above, the device's here (in front of the sample kernel)
-inline int blind_forget_device_backoff(Ctx &c)
-{
-	if (c.boff_forget && c.seg.p) {
-		HIP_TRY(hipMemsetAsync(&((SegCtl *)c.seg.p)->boff_skip, 0, 2 * sizeof(u32), c.stream));
-		c.boff_forget = false;
-	}
-	return RSX_OK;
-}
-// Where the keys-only sorts without a histogram end: 2^30 keys (32-bit offsets in the leaf and tile tables; level-2 slots of more
-// than 32 Ki whole keys have no leaf) -- or, 4-byte keys in two-byte slots (rsx_leafc.hpp: slots of up to 40960 values), where the
-// mean level-2 slot passes 32 Ki: 2^31 + 65536 keys.  Every offset of such a sort still fits 32 bits: 257 level-1 slots of
-// 1.25 x 2^23 keys, 65537 level-2 slots of 40960 values, positions below 2^32.
-template <typename KT> size_t blind_keys_end()
-{
-	if (sizeof(KT) == 4 && dense_cap_max<KT>() >= LEAFC_CAP)
-		return (size_t)32769 << 16;
-	return (size_t)1 << 30;
-}
-template <typename KT> bool blind_wanted(Ctx &c, size_t n, size_t payload_bytes = 0, bool rank = false)
-{
-	if constexpr (sizeof(KT) < 4)
-		return false;
-	if (env().no_blind || env().no_slack || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() ||
-	    c.small.external || env().no_speculation)
-		return false;
-	if (n < ((size_t)1 << 22) || n >= (payload_bytes || rank ? (size_t)1 << 30 : blind_keys_end<KT>()))
-		return false;
-	if (payload_bytes) {
-		// 4-byte keys with 4-byte payloads, 16 Mi .. 2^28 pairs.  Round 3: from 96 Mi (one leaf shape, 5120 pairs, whose fixed
-		// costs made 16 Mi pairs cost 0.63 ms); with the leaves' three shapes (pairs_blind) -- f32 keys -> ranks / pairs, ms,
-		// against one pass per column: 16 Mi 0.271 / 0.273 against 0.271 / 0.299, 32 Mi 0.41 / 0.44 against 0.47 / 0.52, 64 Mi
-		// 0.68 / 0.74 against 0.84 / 1.00, 2^27 1.21 / 1.33 (round 3's shape: 1.54 / 1.63)
-		// (tools/rank_threshold_probe.py, profiles/r04/rank_threshold_probe.txt); a lower RSX_TWO_LEVEL_MIN_LOG2 (tests) lowers the floor
-		// With a wave per leaf for slots of up to 256 / 512 pairs (LeafKCfg<64, 256, 8, 9>, <64, 512, 8, 10>): from 4 Mi pairs -- 8 Mi 0.169 / 0.170 against
-		// 0.176 / 0.177 ms, 10 Mi 0.180 / 0.186 against 0.229 / 0.233, 12 Mi 0.194 / 0.201 against 0.240 / 0.248.
-		// Round 6: up to 2^29 pairs (slots of 10240 pairs: LeafKCfg<1024, 10240, 4, 13>, fourteen position bits)
-		if (sizeof(KT) != 4 || payload_bytes != 4 || n > ((size_t)1 << 29) ||
-		    n < std::min((size_t)1 << 22, (size_t)1 << env().two_level_min_log2))   // (4 Mi: 140 against 151 us, 6 Mi 148 against 161)
-			return false;
-	} else {
-		// keys only: without the histogram two levels beat one pass per column earlier than with it.  8-byte keys from 4.5 Mi
-		// keys on (a wave per leaf for slots of up to 256 keys, LeafKCfg<64, 256, 8, 9>: 5 Mi 204 against 278 us, 7 Mi 219 against
-		// 322, 8 Mi 234 where 128 threads per leaf took 284; five kept columns: 4 Mi 172 against 167, 5 Mi 184 against 207;
-		// one level reaches 3-4 Mi keys: tools/u64_small_probe.py), before that from 8 Mi
-		// keys on since their leaves come in three shapes (launch_leaves; one shape: from 48 Mi) -- uniform keys 8 Mi 0.287
-		// against 0.347 ms, 16 Mi 0.386 against 0.605, 32 Mi 0.58 against 1.18, 64 Mi 0.93 against 2.15; five kept columns: 8 Mi
-		// level, 16 Mi 0.337 against 0.404 (tools/u64_threshold_probe.py, profiles/r04/u64_threshold_probe.txt).
-		// 4-byte keys, round 4 (their leaves read two-byte slots and are one wave's -- or a row of sixteen lanes' -- work up to
-		// 1024 values, rsx_leaf16w_kernel / rsx_leaf16q_kernel): from 7.5 Mi keys (8 Mi 128 against 137 us, tools/size_sweep.py)
-		size_t floor_keys = sizeof(KT) == 8 ? (size_t)9 << 19 : (size_t)15 << 19;
-		if (env().blind_min_log2)
-			floor_keys = (size_t)1 << env().blind_min_log2;
-		floor_keys = std::min(floor_keys, (size_t)1 << env().two_level_min_log2);
-		if (n < floor_keys)
-			return false;
-	}
-	blind_refresh(c);
-	const int kind = blind_kind<KT>(payload_bytes, rank);
-	if (c.blind_skip[kind]) {
-		--c.blind_skip[kind];
-		return false;
-	}
-	return true;
-}
-
-// The device's part: the sample, both passes, the tables and the leaves, enqueued; *enqueued = 0: no room for the slots (or no
-// leaf shape for them): nothing was enqueued.  Nothing waits for the host; SegCtl::mode == SEG_MODE_LEAVES (and the pinned
-// copy the slack plan writes) says afterwards whether the sort went through.
-// ... for a device-scheduled sort (rsx_sort_inplace_async): the same sizes; its back-off lives on the device (SegCtl::boff_skip: nothing is ever read back)
-template <typename KT> bool async_blind_ok(Ctx &c, size_t n)
-{
-	if constexpr (sizeof(KT) < 4)
-		return false;
-	// (a caller's workspace: only one that was sized for the slots as well, rsx_workspace_bytes_fast)
-	if (env().no_blind || env().no_slack || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() ||
-	    (c.small.external && !c.ws_blind) || env().no_speculation)
-		return false;
-	// (blind_wanted's floors, except that 4-byte keys start at 9 Mi here: at 8 Mi the empty launches of the gated histogram-first
-	// kernels behind the attempt make it 153 us against 138 for one pass per column; the blocking sort: 127 against 135-139)
-	size_t floor_keys = sizeof(KT) == 8 ? (size_t)1 << 23 : (size_t)9 << 20;
-	if (env().blind_min_log2)
-		floor_keys = (size_t)1 << env().blind_min_log2;
-	floor_keys = std::min(floor_keys, (size_t)1 << env().two_level_min_log2);
-	blind_refresh(c);
-	return n >= std::max(floor_keys, (size_t)1 << 22) && n < (c.ws_blind ? (size_t)1 << 30 : blind_keys_end<KT>());
-}
-// ... for key + payload and rank sorts (4-byte keys, 4-byte payloads: blind_wanted's window, without its back-off)
-template <typename KT> bool async_pairs_blind_ok(Ctx &c, size_t n, size_t payload_bytes)
-{
-	if (sizeof(KT) != 4 || payload_bytes != 4)
-		return false;
-	if (env().no_blind || env().no_slack || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() || c.small.external ||
-	    env().no_speculation)
-		return false;
-	blind_refresh(c);
-	return n >= std::min((size_t)1 << 24, (size_t)1 << env().two_level_min_log2) && n >= ((size_t)1 << 22) && n <= ((size_t)1 << 29);
-}
-
-template <typename KT>
-int blind_enqueue(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, int *enqueued)
-{
-	typedef Sc2Cfg<KT, NoVal> C2;
-	*enqueued = 0;
-	const u32 mean1 = (u32)(n >> 8), mean2 = (u32)(n >> 16);
-	const u32 cap1 = level1_slot_cap<KT>(mean1);
-	const u32 cap2 = slot_cap_for(mean2);
-	if (cap2 > std::max((u32)LeafShapes<KT>::Big::CAP, dense_cap_max<KT>()))
-		return RSX_OK;
-	if (c.blind_no_room)
-		return RSX_OK;
-	// Where the level-1 slots lie.  The attempt only writes after its sample has PROVEN the input unsorted and four columns kept
-	// -- from then on the caller's second buffer belongs to the sort whatever route finishes it (radix_sort.hpp:60-62 keeps it
-	// untouched only on the early exits) -- so the slots that fit there (n / cap1 of them: 204 of 256) lie there and the library
-	// allocates the rest only: 0.25 n keys instead of 1.25 n (2^28 u32 keys: 0.25 GiB + 0.63 GiB of two-byte level-2 slots
-	// instead of 1.25 + 1.25).  Needs a slot that holds a tile (a lost attempt's runs go over the slot's own beginning there,
-	// rsx_scatter2.hpp); RSX_NO_AUX_SLOTS=1: all slots in scratch memory.
-	u32 lo = (aux && !env().no_aux_slots && cap1 >= (u32)C2::TILE) ? (u32)std::min<size_t>(n / cap1, 255) : 0u;
-	c.slack_cap = cap2;   // (dense_slots asks for it)
-	c.slack_mean = mean2;
-	const size_t slot2_bytes = dense_slots<KT>(c) ? 2 : sizeof(KT);
-	if (c.slack1.ensure(((size_t)(256 - lo) * cap1 + C2::TILE) * sizeof(KT)) != RSX_OK ||
-	    c.slack.ensure(((size_t)65536 * cap2 + C2::TILE) * slot2_bytes) != RSX_OK) {
-		// no room for the slots: the ordinary path, now and for this context's later sorts (a multi-GiB hipMalloc that fails
-		// is not worth repeating per sort); what was allocated of the pair goes back -- unless this is a device-scheduled sort
-		// (AsyncScope): a graph captured earlier may name the old arrays, so nothing is released and nothing is remembered
-		(void)hipGetLastError();
-		c.slack1_cap = c.slack_cap = 0;
-		if (!g_in_async) {
-			c.slack1.release();
-			c.slack.release();
-			c.blind_no_room = true;
-		}
-		return RSX_OK;
-	}
-	if (lo) {
-		// the level-1 pass reaches both parts with 32-bit element offsets from the lower one (rsx_scatter2.hpp, SegArgs): they
-		// must lie within 2^32 elements of each other, the dump area behind the last slot included -- else everything in scratch
-		const uintptr_t lo_a = (uintptr_t)aux, hi_a = (uintptr_t)c.slack1.p - (size_t)lo * cap1 * sizeof(KT);
-		const uintptr_t span = (std::max(lo_a, hi_a) - std::min(lo_a, hi_a)) / sizeof(KT) + (size_t)257 * cap1 + C2::TILE;
-		if (span >= ((uintptr_t)1 << 32)) {
-			lo = 0;
-			if (c.slack1.ensure(((size_t)256 * cap1 + C2::TILE) * sizeof(KT)) != RSX_OK) {
-				(void)hipGetLastError();
-				c.slack1_cap = c.slack_cap = 0;
-				if (!g_in_async) {
-					c.slack1.release();
-					c.slack.release();
-					c.blind_no_room = true;
-				}
-				return RSX_OK;
-			}
-		}
-	}
-	c.slack1_lo = lo;
-	RSX_TRY(seg_layout<KT>(c, n));
-	RSX_TRY(c.gscan.ensure(256 * sizeof(u64)));
-	const u64 ntiles0 = (n + C2::TILE - 1) / C2::TILE;
-	const size_t st_bytes = 256 + (ntiles0 + seg_extra_rows<KT>()) * 256 * 4;
-	SegCtl *ctl = (SegCtl *)c.seg.p;
-	SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-	LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
-	u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
-	u64 *off1 = (u64 *)c.gscan.p;
-	// (a context in a caller's workspace has neither a pinned control block nor an event: nobody reads a verdict there)
-	if (!c.seg_ev && !c.small.external)
-		HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
-	if (c.host_segctl)
-		c.host_segctl->mode = SEG_MODE_NONE;
-	c.slack1_cap = cap1;
-	c.slack_cap = cap2;
-	// 4-byte keys from 64 Mi keys on: the level-1 pass in whole 64-byte atoms (rsx_pass32a_kernel: a workgroup per CU takes a range
-	// of tiles and carries what does not fill an atom; a bucket then lies at both ends of its slot)
-	const bool atoms = pass16a_wanted<KT>(c);   // (the level-2 pass that writes whole atoms: smaller tiles, two cursors per slot)
-	const bool atoms64 = pass64a_narrow_wanted<KT>(c);   // (8-byte keys: the same for the form that writes four-byte slots; the sample decides which form runs)
-	typedef Pass32aCfgT<sizeof(KT) == 8 ? 14 : 28> P32;
-	const size_t min32 = env().pass32_min_mi ? (size_t)env().pass32_min_mi << 20 : sizeof(KT) == 8 ? (size_t)3 << 23 : (size_t)13 << 22;
-	const bool atoms1 = (sizeof(KT) == 4 ? atoms : !env().no_unstable) && !env().no_pass32a && n >= min32 &&
-	                    cap1 >= (u32)P32::TILE + 2 * PASS32_BACK;
-	// (keys the caller says arrive in order of their top digit, piece by piece: four counters per digit, rsx_pass32.hpp)
-	const bool rep4 = (c.hints & 1u) != 0 || (env().probe & 4u) != 0;
-	// 8-byte keys in which nothing below the level-1 digit varies above bit 32 (keys below 2^40: BASELINE.json's cfg 3 (ii), (iii)):
-	// the level-1 slots can hold low words -- all 256 of them then fit the caller's second buffer -- and the level-2 pass reads four
-	// bytes per key.  Both atom passes in both forms are enqueued; the sample decides (SegCtl::narrow == 2).  The 256 slots of cap1
-	// four-byte places must fit the caller's n keys (a larger cap1 -- RSX_CAP1_PAD_KIB -- would write past its end).
-	c.narrow1 = sizeof(KT) == 8 && atoms1 && atoms64 && lo != 0 && !rep4 && !env().no_narrow1 && (((uintptr_t)aux) & 63) == 0 &&
-	            (size_t)256 * cap1 * 4 <= n * sizeof(KT);
-	// the sample (workgroup 0: control block, plan) and the zeroing of both passes' status words, one launch
-	static_assert(sizeof(SegCtl) <= 256, "the control block is not part of what is zeroed");
-	RSX_TRY(blind_forget_device_backoff(c));
-	hipLaunchKernelGGL((rsx_blind_precheck_kernel<KT>), dim3(1 + 512), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, ka, ctl,
-	                   c.plan(), c.dev_host_plan, (u32x4 *)((char *)c.seg.p + c.seg_status_off), (u64)(2 * st_bytes / 16),
-	                   4u,   // (two levels want four kept columns: two for the passes, two or more for the leaves)
-	                   // 4-byte keys whose leaves read two-byte slots (rsx_leaf16.hpp): the MSB digits may lie below constant top bits
-	                   (u32)(sizeof(KT) == 4 && dense_slots<KT>(c) && !env().no_leaf16 && !env().no_shift ? 1 : 0),
-	                   // 8-byte keys in slots rsx_leafk_kernel takes: four-byte slots where the leaves' columns lie in the low word
-	                   (u32)(narrow_slots_ok<KT>(cap2) ? (c.narrow1 ? 2 : 1) : 0), 0u,
-	                   // a device-scheduled sort keeps its back-off on the device (SegCtl::boff_skip); the blocking sorts keep theirs on the host
-	                   (u32)(g_in_async ? 1 : 0), (u32)((env().probe & 4u) ? 1u : c.hints));
-	{
-		// 4-byte keys: only in front of rsx_pass16a_kernel (a bucket that lies at both ends of its slot is one tile more: that pass's
-		// tile table has room for it); from 52 Mi keys, where that pass starts for good -- as first built (the next tile requested
-		// ahead, two LDS atomics per key) it was level with the chained pass at 64-80 Mi and 1 % ahead at 96 Mi
-		// (profiles/r05/atoms_threshold_probe.txt); as it is now: 0-4 % ahead at 54 .. 95 Mi keys, never behind
-		// (tools/ab_sizes.py RSX_PASS32_MIN_MI 96 40 u32 ...), 2-5 % behind in the 1024-value-slot window around 40 Mi.
-		// 8-byte keys (atoms of eight keys, 14 Ki-key tiles): in front of the CHAINED level-2 pass, whose status words have a row
-		// more per bucket for that (seg_extra_rows); from 24 Mi keys (1.3-2.5 % ahead at 24 .. 44 Mi, level at 20 Mi:
-		// tools/ab_sizes.py RSX_PASS32_MIN_MI 48 16 u64 ...) -- tools/ubench/pass32_probe, 2^28 u64 keys: 0.926 ms against 1.01 for
-		// the chained pass, 2^27: 0.447 against 0.50.
-		if (atoms1) {
-			// one base for the stores, the parts' offsets in the slots' places (as launch_seg_pass does for the chained pass)
-			u32 off_lo = 0, off_hi = 0;
-			KT *kbase = (KT *)c.slack1.p;
-			if (lo) {
-				const uintptr_t lo_a = (uintptr_t)aux, hi_a = (uintptr_t)c.slack1.p - (size_t)lo * cap1 * sizeof(KT);
-				const uintptr_t base_a = std::min(lo_a, hi_a);
-				off_lo = (u32)((lo_a - base_a) / sizeof(KT));
-				off_hi = (u32)((hi_a - base_a) / sizeof(KT));
-				kbase = (KT *)base_a;
-			}
-			u32 *cur1 = (u32 *)((char *)c.seg.p + c.seg_status_off + st_bytes + 256);
-			u32 *ovf = &((SegCtl *)c.seg.p)->overflow;
-			const bool plain = ka.fmask == 0 && ka.sflip == 0 && ka.desc == 0;
-			ProfScope prof(1, (u64)n * 2 * sizeof(KT), c.stream);
-			// (probed and not kept: Pass32aCfgT<12> -- 12 Ki-key tiles, 81 KB of LDS, two workgroups per CU, no prefetch: 0.534-0.543 ms
-			// for 2^28 keys where this shape takes 0.470-0.477 on the same box, profiles/r05/pass32a_probe.txt)
-			// (the next tile's keys requested while this tile is written out: 1 % ahead at 2^27 keys, 2-5 % BEHIND from 2^28 on -- the
-			// level-1 pass of 2^28 keys 0.485 -> 0.457 ms without, three rounds alternating in one process, tools/blind_ab.py;
-			// 380 M keys 1.975 -> 1.929 ms, 2^30 5.157 -> 5.130: reads and writes in flight together cost more than the gap between tiles)
-			// (8-byte keys: never ahead -- 2^27 keys 0.447 against 0.455 ms, 2^28 0.926 against 0.951)
-			// (later, with one LDS atomic per key: never ahead at 54 .. 224 Mi keys either -- 54 Mi 0.340 -> 0.330 ms, 192 Mi 0.983 -> 0.961,
-			// level at 80 and 128 Mi, tools/ab_sizes.py RSX_PASS32_PREFETCH 1 0 u32 ...: off unless RSX_PASS32_PREFETCH=1 asks for it)
-			const bool prefetch = sizeof(KT) == 4 && env().pass32_prefetch > 0;
-#define RSX_LAUNCH_P32R(DIGV, PF, REPV)                                                                                      \
-			hipLaunchKernelGGL((rsx_pass32a_kernel<KT, DIGV, PF, P32, REPV>), dim3(256), dim3(P32::BLOCK), 0, c.stream,              \
-			                   (const KT *)src, (u64)n, kbase, lo, off_lo, off_hi, cap1, (const SegCtl *)ctl, cur1, ovf, ka)
-#define RSX_LAUNCH_P32(DIGV, PF)                                                                                             \
-			do {                                                                                                                 \
-				if (rep4 && !(PF))                                                                                               \
-					RSX_LAUNCH_P32R(DIGV, false, 4);                                                                             \
-				else                                                                                                             \
-					RSX_LAUNCH_P32R(DIGV, PF, 1);                                                                                \
-			} while (0)
-			if constexpr (sizeof(KT) == 4) {
-				if (plain && prefetch)
-					RSX_LAUNCH_P32(DIG_PLAIN, true);
-				else if (!plain && prefetch)
-					RSX_LAUNCH_P32(DIG_GENERIC, true);
-			}
-			if (plain && !prefetch)
-				RSX_LAUNCH_P32(DIG_PLAIN, false);
-			else if (!prefetch)
-				RSX_LAUNCH_P32(DIG_GENERIC, false);
-#undef RSX_LAUNCH_P32
-#undef RSX_LAUNCH_P32R
-			if constexpr (sizeof(KT) == 8) {
-				if (c.narrow1) {
-					// ... and the form that writes low words: slot d = cap1 four-byte places at d x cap1 of the caller's second buffer
-					if (plain)
-						hipLaunchKernelGGL((rsx_pass32a_kernel<KT, DIG_PLAIN, false, P32, 1, u32>), dim3(256), dim3(P32::BLOCK), 0, c.stream,
-						                   (const KT *)src, (u64)n, (u32 *)aux, 256u, 0u, 0u, cap1, (const SegCtl *)ctl, cur1, ovf, ka);
-					else
-						hipLaunchKernelGGL((rsx_pass32a_kernel<KT, DIG_GENERIC, false, P32, 1, u32>), dim3(256), dim3(P32::BLOCK), 0, c.stream,
-						                   (const KT *)src, (u64)n, (u32 *)aux, 256u, 0u, 0u, cap1, (const SegCtl *)ctl, cur1, ovf, ka);
-				}
-			}
-			HIP_TRY(hipGetLastError());
-		}
-	}
-	if (!atoms1)
-		RSX_TRY(launch_seg_pass<KT>(c, src, lo ? aux : nullptr, n, ka, -2, 1));
-	hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
-	                   atoms ? (u32)Pass16aCfg::TILE : (u32)C2::TILE, tiles, ctl, btile, off1, cap1,
-	                   (const u32 *)((char *)c.seg.p + c.seg_status_off + st_bytes + 256), (u32)ntiles0, atoms1 ? PASS32_BACK : 0u,
-	                   atoms64 ? (u32)Pass2wCfg<u32>::TILE : 0u, c.narrow1 ? (u32)Pass64aCfgLow::TILE : 0u);
-	RSX_TRY(launch_seg_pass<KT>(c, lo ? aux : nullptr, nullptr, n, ka, -2, 2));
-	hipLaunchKernelGGL((rsx_seg_slack_plan_kernel<u32>), dim3(256), dim3(256), 0, c.stream,
-	                   (const u32 *)((char *)c.seg.p + c.seg_status_off + 256), (const u32 *)btile, (const u64 *)c.ghist(),
-	                   (const Plan *)c.plan(), ctl, segtab, cap2, c.dev_host_segctl, (const u64 *)off1,
-	                   (atoms ? 2u : atoms64 ? 3u : 1u) | ((env().probe & 1u) << 8));
-	HIP_TRY(hipGetLastError());
-	if (c.seg_ev)
-		HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-	u32 leaf_shape = LeafShapes<KT>::shape_for_slots(cap2);
-	if (dense_slots<KT>(c))
-		leaf_shape |= 0x100u;   // (the leaves read 2-byte slots: the cut shapes have that variant)
-	if (sizeof(KT) == 8 && cap2 <= 5120u)
-		leaf_shape |= 0x200u;   // (8-byte keys in slots of up to 5120: rsx_leafk_kernel)
-	RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_TWO_LEVEL, leaf_shape, (const u64 *)off1));
-	*enqueued = 1;
-	return RSX_OK;
-}
-
-template <typename KT>
-int sort_keys_blind(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, KT **result, rsx_info *info, int *done)
-{
-	*done = 0;
-	int enqueued = 0;
-	const size_t pmark = prof_mark();
-	RSX_TRY(blind_enqueue<KT>(c, src, aux, n, ka, &enqueued));
-	if (!enqueued)
-		return RSX_OK;
-	HIP_TRY(hipEventSynchronize(c.seg_ev));
-	if (c.host_segctl->mode != SEG_MODE_LEAVES) {
-		blind_called_off(c, blind_kind<KT>(0));
-		c.slack_cap = 0;
-		prof_called_off(pmark, c.stream);
-		return RSX_OK;
-	}
-	c.blind_backoff[blind_kind<KT>(0)] = 0;
-	if (sizeof(KT) == 8 && c.host_segctl->narrow) {
-		// the sample chose four-byte level-2 slots (SegCtl::narrow): the level-2 pass wrote 4 bytes per key, the leaves read 4
-		// (narrow == 2: the level-1 slots hold four bytes per key too)
-		const bool n1 = c.host_segctl->narrow == 2u;
-		prof_rebook(pmark, c.stream, 2, (u64)n * (4 + sizeof(KT)));
-		prof_rebook(pmark, c.stream, 1, (u64)n * ((n1 ? 4 : sizeof(KT)) + 4), 3);   // (the whole-key form of the level-2 pass returned at once)
-		if (n1)
-			prof_rebook(pmark, c.stream, 1, (u64)n * (sizeof(KT) + 4));            // (what is left of kind 1: the level-1 pass)
-	}
-	const Plan plan = *c.host_plan;
-	info_from_plan(info, plan);
-	KT *final = (plan.ncols & 1) ? aux : src;   // radix_sort.hpp:92
-	*result = final;
-	if (info) {
-		info->result_in_aux = final == aux;
-		info->hybrid = 5u;
-	}
-	*done = 1;
-	return RSX_OK;
-}
-
 // ---- 8-byte keys by (bit length, mantissa) digits: rsx_logroute.hpp ----------------------------------------------------------
 // Tried where the sorts without a histogram do not go (their sample said no, or they are backing off): the route's own sample
 // says at once whether it is worth the histogram; everything behind it is device-scheduled and the verdict is read once.
@@ -1692,14 +611,8 @@ int sort_keys_device_impl(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int ord
 			RSX_TRY(plan_wait(c, &plan));
 			info_from_plan(info, plan);
 			RSX_TRY(capture_hist(c, n, sizeof(KT)));
-			if (plan.sorted) {                   // radix_sort.hpp:60-62
-				if (info) {
-					info->early_exit = 2;
-					info->ncols = 0;
-				}
-				*result = src;
-				return RSX_OK;
-			}
+			if (plan.sorted)                     // radix_sort.hpp:60-62
+				return finish_sorted(info, result, src);
 			*result = aux;                       // one pass: radix_sort.hpp:92
 			if (info)
 				info->result_in_aux = 1;
@@ -1760,14 +673,8 @@ int sort_keys_device_impl(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int ord
 			RSX_TRY(plan_wait(c, &plan));
 			info_from_plan(info, plan);
 			RSX_TRY(capture_hist(c, n, sizeof(KT)));
-			if (plan.sorted) {                   // radix_sort.hpp:60-62
-				if (info) {
-					info->early_exit = 2;
-					info->ncols = 0;
-				}
-				*result = src;
-				return RSX_OK;
-			}
+			if (plan.sorted)                     // radix_sort.hpp:60-62
+				return finish_sorted(info, result, src);
 			*result = plan.ncols == 1 ? aux : src;
 			if (info)
 				info->result_in_aux = plan.ncols == 1;
@@ -1828,14 +735,8 @@ int sort_keys_device_impl(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int ord
 		prof_called_off(pmark, c.stream, 2);
 	if (spec && plan.sorted)
 		prof_called_off(pmark, c.stream, 1);
-	if (plan.sorted) {                       // radix_sort.hpp:60-62
-		if (info) {
-			info->early_exit = 2;
-			info->ncols = 0;
-		}
-		*result = src;
-		return RSX_OK;
-	}
+	if (plan.sorted)                         // radix_sort.hpp:60-62
+		return finish_sorted(info, result, src);
 	if (fill_one && plan.ncols == 1) {
 		if (!spec)
 			HIP_TRY(launch_fill());
@@ -1924,8 +825,8 @@ int sort_keys_inplace_async(Ctx &c, KT *buf, KT *scratch, size_t n, int dtype, i
 		}
 	}
 	if (blind)
-		pverdict.attempt_enqueued((const SegCtl *)c.seg.p);
-	c.pass_gate = blind ? (const SegCtl *)c.seg.p : nullptr;
+		pverdict.attempt_enqueued(SegView(c).ctl());
+	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
 	c.async_tried_blind = blind != 0;
 	int rc = plan_phase<KT>(c, buf, n, ka, nullptr, status_total, caps);
 	for (u32 i = 0; i < sizeof(KT) && rc == RSX_OK; ++i)   // pass i = the i-th kept column, if there is one (radix_sort.hpp:83-90)
@@ -1949,10 +850,6 @@ int sort_keys_inplace_async(Ctx &c, KT *buf, KT *scratch, size_t n, int dtype, i
 }
 
 // ---- key + payload, no host synchronisation: as sort_keys_inplace_async, the result always in (k, v) -----------------------
-template <typename KT, typename VT>
-int pairs_blind_enqueue(Ctx &c, const KT *kin, const VT *vin, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, int *enqueued,
-                        KT *kspare = nullptr, VT *vspare = nullptr);
-
 template <typename KT, typename VT>
 int sort_pairs_inplace_async(Ctx &c, KT *k, KT *ks, VT *v, VT *vs, size_t n, int dtype, int order)
 {
@@ -1979,8 +876,8 @@ int sort_pairs_inplace_async(Ctx &c, KT *k, KT *ks, VT *v, VT *vs, size_t n, int
 			RSX_TRY((pairs_blind_enqueue<KT, VT>(c, k, v, k, v, n, ka, &blind, ks, vs)));
 	}
 	if (blind)
-		pverdict.attempt_enqueued((const SegCtl *)c.seg.p);
-	c.pass_gate = blind ? (const SegCtl *)c.seg.p : nullptr;
+		pverdict.attempt_enqueued(SegView(c).ctl());
+	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
 	c.async_tried_blind = blind != 0;
 	int rc = plan_phase<KT>(c, k, n, ka, nullptr, status_total);
 	for (u32 i = 0; i < sizeof(KT) && rc == RSX_OK; ++i)
@@ -1993,386 +890,6 @@ int sort_pairs_inplace_async(Ctx &c, KT *k, KT *ks, VT *v, VT *vs, size_t n, int
 	hipLaunchKernelGGL(rsx_copy_if_odd_kernel, dim3(2048), dim3(256), 0, c.stream, (unsigned char *)v, (const unsigned char *)vs,
 	                   (u64)n * sizeof(VT), (const Plan *)c.plan());
 	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// ---- two MSB passes and leaves for key + payload sorts and rank sorts (4-byte keys, 4-byte payloads; rsx_leaf_pairs_kernel) ----
-template <typename KT> HybCaps hybrid_caps_pairs(size_t n, size_t val_bytes_, bool counted_too)
-{
-	HybCaps caps{0, 0, 0, 0};
-	if (sizeof(KT) != 4 || val_bytes_ != 4 || !hybrid_enabled())
-		return caps;
-	// one level where every bucket of the highest kept column fits the pairs' leaf (5120 pairs: up to about a million pairs)
-	caps.cap1 = 5120;
-	caps.min_cols1 = 3;
-	// two levels: the slack route, and only where a slot fits the pairs' leaf shape: 2^27 .. 2^28 pairs (cfg 4); key + payload
-	// sorts (counted_too) with RSX_NO_SLACK=1: the second pass counted first, as for keys alone (pairs_two_level)
-	if ((!env().no_slack || counted_too) && n >= ((size_t)1 << env().two_level_min_log2) && n <= ((size_t)1 << 28)) {
-		caps.cap2 = (u32)LeafShapes<KT>::Small::CAP;
-		caps.min_cols2 = 4;
-	}
-	return caps;
-}
-
-// Pass 1 (by the highest kept column) has written (k1, v1).  The second pass goes into slots, the leaves write the payloads
-// (and the keys, if kfinal) to (kfinal, vfinal).  *ok = false: a slot overflowed -- nothing the caller owns was written, it
-// sorts with one pass per column.
-// RSX_NO_SLACK=1 (key + payload sorts only: kdense / vdense are their first buffers, which pass 1 has read): the counted second
-// pass of sort_keys_two_level -- the level-2 column counted per bucket (rsx_seg_hist1_kernel), the pass (k1, v1) -> (kdense,
-// vdense) at those offsets, the leaves on the dense buckets.  *ok = false: a (digit, digit) bucket does not fit the pairs' leaf --
-// known before the pass is enqueued, nothing but (k1, v1) has been written.
-template <typename KT, typename VT>
-int pairs_two_level(Ctx &c, const KT *k1, const VT *v1, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, bool *ok,
-                    KT *kdense = nullptr, VT *vdense = nullptr)
-{
-	typedef Sc2Cfg<KT, VT> C2;
-	typedef LeafCfg<u32, 4, 20, 3> L;   // 5120 pairs: the slack slot of 2^28 pairs; three workgroups per CU
-	*ok = false;
-	const u64 rows = (n + C2::TILE - 1) / C2::TILE + 256;
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	const size_t hist_bytes = (size_t)256 * (sizeof(KT) - 1) * 256 * sizeof(u32);
-	c.seg_hist_off = 256;
-	c.seg_status_off = c.seg_hist_off + hist_bytes;
-	c.seg_segtab_off = c.seg_status_off + (sizeof(KT) - 1) * st_bytes;
-	c.seg_tiles_off = c.seg_segtab_off + 65536 * sizeof(LeafSeg);
-	c.seg_btile_off = c.seg_tiles_off + rows * sizeof(SegTile);
-	{
-		const void *before = c.seg.p;
-		RSX_TRY(c.seg.ensure(c.seg_btile_off + 257 * sizeof(u32)));
-		if (c.seg.p != before)
-			HIP_TRY(hipMemsetAsync(c.seg.p, 0, 256, c.stream));
-	}
-	if (env().no_slack) {
-		if (!kdense || !vdense || !kfinal)
-			return RSX_OK;
-		SegCtl *ctl = (SegCtl *)c.seg.p;
-		u32 *seghist = (u32 *)((char *)c.seg.p + c.seg_hist_off);
-		SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-		LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
-		u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
-		if (!c.seg_ev)
-			HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
-		c.host_segctl->mode = SEG_MODE_NONE;
-		HIP_TRY(hipMemsetAsync(c.seg.p, 0, c.seg_status_off + st_bytes, c.stream));
-		hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
-		                   (u32)C2::TILE, tiles, ctl, btile);
-		{
-			ProfScope prof(0, (u64)n * sizeof(KT), c.stream);
-			hipLaunchKernelGGL((rsx_seg_hist1_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, k1, (const SegTile *)tiles, (const SegCtl *)ctl,
-			                   (const Plan *)c.plan(), ka, seghist);
-		}
-		hipLaunchKernelGGL((rsx_seg_plan_kernel<KT>), dim3(256), dim3(256), 0, c.stream, seghist, (const u64 *)c.ghist(), (u64)n,
-		                   (const Plan *)c.plan(), ctl, segtab, (u32)L::CAP, c.dev_host_segctl, 0u);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-		HIP_TRY(hipEventSynchronize(c.seg_ev));
-		if (c.host_segctl->mode != SEG_MODE_LEAVES)
-			return RSX_OK;
-		char *base = (char *)c.seg.p + c.seg_status_off;
-		SegArgs sa{};
-		sa.ctl = ctl;
-		sa.hist = (const u32 *)seghist;
-		sa.tiles = tiles;
-		sa.slots = (u32)sizeof(KT) - 1;
-		sa.overflow = &ctl->overflow;
-		{
-			ProfScope prof(1, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
-			hipLaunchKernelGGL((rsx_scatter2_kernel<KT, VT, u32, C2, false, DIG_GENERIC, false, KT, true>), dim3((unsigned)rows),
-			                   dim3(C2::BLOCK), 0, c.stream, k1, kdense, v1, vdense, (u64)n, 0u, (const u64 *)c.ghist(), 1u,
-			                   (u32 *)(base + 256), (u32 *)base, ka, (u32)SCATTER_SEG_LEAVES, (u64 *)nullptr, (const Plan *)c.plan(), 0u, 0u,
-			                   (const u32 *)nullptr, sa);
-		}
-		{
-			ProfScope prof(2, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
-			hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L>), dim3(env().leaf_grid), dim3(L::BLOCK), 0, c.stream, (const KT *)kdense,
-			                   (const VT *)vdense, 0u, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab, (const SegCtl *)ctl,
-			                   ka);
-		}
-		HIP_TRY(hipGetLastError());
-		*ok = true;
-		return RSX_OK;
-	}
-	const u32 mean = (u32)(n >> 16);
-	const u32 cap = slot_cap_for(mean);
-	if (cap > (u32)L::CAP)
-		return RSX_OK;
-	if (c.slack.ensure(((size_t)65536 * cap + C2::TILE) * sizeof(KT)) != RSX_OK ||
-	    c.slack_v.ensure(((size_t)65536 * cap + C2::TILE) * sizeof(VT)) != RSX_OK) {
-		(void)hipGetLastError();
-		return RSX_OK;   // (no room for the slots: one pass per column)
-	}
-	SegCtl *ctl = (SegCtl *)c.seg.p;
-	SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-	LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
-	u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
-	if (!c.seg_ev)
-		HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
-	HIP_TRY(hipMemsetAsync(c.seg.p, 0, c.seg_status_off + st_bytes, c.stream));
-	hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
-	                   (u32)C2::TILE, tiles, ctl, btile);
-	char *base = (char *)c.seg.p + c.seg_status_off;
-	SegArgs sa{};
-	sa.ctl = ctl;
-	sa.hist = (const u32 *)((char *)c.seg.p + c.seg_hist_off);
-	sa.tiles = tiles;
-	sa.slots = (u32)sizeof(KT) - 1;
-	sa.slack_cap = cap;
-	sa.overflow = &ctl->overflow;
-	{
-		ProfScope prof(1, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
-		hipLaunchKernelGGL((rsx_scatter2_kernel<KT, VT, u32, C2, false, DIG_GENERIC, false, KT, true>), dim3((unsigned)rows),
-		                   dim3(C2::BLOCK), 0, c.stream, k1, (KT *)c.slack.p, v1, (VT *)c.slack_v.p, (u64)n, 0u, (const u64 *)c.ghist(), 1u,
-		                   (u32 *)(base + 256), (u32 *)base, ka, (u32)SCATTER_SEG_SLACK, (u64 *)nullptr, (const Plan *)c.plan(), 0u, 0u,
-		                   (const u32 *)nullptr, sa);
-	}
-	hipLaunchKernelGGL((rsx_seg_slack_plan_kernel<u32>), dim3(256), dim3(256), 0, c.stream, (const u32 *)(base + 256), (const u32 *)btile,
-	                   (const u64 *)c.ghist(), (const Plan *)c.plan(), ctl, segtab, cap, c.dev_host_segctl);
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-	{
-		ProfScope prof(2, (u64)n * (sizeof(KT) + 2 * sizeof(VT) + (kfinal ? sizeof(KT) : 0)), c.stream);
-		hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L>), dim3(env().leaf_grid), dim3(L::BLOCK), 0, c.stream, (const KT *)c.slack.p,
-		                   (const VT *)c.slack_v.p, cap, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab,
-		                   (const SegCtl *)ctl, ka);
-	}
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventSynchronize(c.seg_ev));
-	*ok = c.host_segctl->mode == SEG_MODE_LEAVES;
-	return RSX_OK;
-}
-
-// One MSB pass has written (k1, v1); the 256 buckets' pairs sorted by the remaining columns into (kfinal, vfinal).
-template <typename KT, typename VT>
-int pairs_one_level(Ctx &c, const KT *k1, const VT *v1, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka)
-{
-	typedef LeafCfg<u32, 4, 20, 3> L;
-	ProfScope prof(2, (u64)n * (sizeof(KT) + 2 * sizeof(VT) + (kfinal ? sizeof(KT) : 0)), c.stream);
-	hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L>), dim3(256), dim3(L::BLOCK), 0, c.stream, k1, v1, 0u, kfinal, vfinal,
-	                   (const Plan *)c.plan(), (const LeafSeg *)nullptr, (const SegCtl *)nullptr, ka, (u32)HYB_ONE_LEVEL,
-	                   (const u64 *)c.ghist(), (u64)n);
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// Rank sorts and key + payload sorts without the histogram (sort_keys_blind's scheme with the (key, payload) pass kernel and
-// the pairs' leaves): both MSB passes into slots -- the first reads the caller's (kin, vin), or makes the indices (vin ==
-// nullptr) --, the leaves write to (kfinal, vfinal).  *done = 0: called off, nothing the caller owns has been written.
-template <typename KT, typename VT>
-int pairs_blind_enqueue(Ctx &c, const KT *kin, const VT *vin, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, int *enqueued,
-                        KT *kspare, VT *vspare)
-{
-	typedef Sc2Cfg<KT, VT> C2;
-	typedef LeafCfg<u32, 4, 20, 3> L;
-	// The level-2 slots hold the low two bytes of what the level-2 pass reads (derived keys, or the packed keys of SegCtl::compact):
-	// the two MSB passes have decided every bit above them, and no leaf ever looked at more of a key (rsx_leafp_kernel, K16)
-	typedef unsigned short K2;
-	static_assert(sizeof(KT) == 4, "two MSB digits above two bytes");
-	*enqueued = 0;
-	const u32 mean1 = (u32)(n >> 8), mean2 = (u32)(n >> 16);
-	const u32 cap1 = slot_cap_for(mean1), cap2 = slot_cap_for(mean2);
-	typedef LeafCfg<u32, 16, 12, 1> LB;          // ... and up to 12288 (slots of 10240 pairs: 2^28 .. 2^29 pairs), one workgroup per CU
-	typedef LeafKCfg<1024, 10240, 4, 13> P10;   // the compound leaves' shape for those slots
-	if (cap2 > (u32)P10::CAP)
-		return RSX_OK;
-	const bool big = cap2 > (u32)L::CAP || env().pairs_leaf_big;
-	if (c.blind_no_room)
-		return RSX_OK;
-	// Where the level-1 slots lie (as blind_enqueue: nothing is written before the sample has proven the input unsorted and every
-	// column kept, after which the caller's spare buffers belong to the sort whatever route finishes it).  `kspare` / `vspare`: n
-	// elements each that the attempt may use -- the second key and payload buffers of a key + payload sort; of a rank sort the
-	// two halves of its index buffer (the first for the indices until the leaves write it, the second, through which the
-	// reference's passes ping-pong, for the 4-byte keys).  The slots that fit (n / cap1 of them: 204 of 256) lie there, the
-	// others in scratch; keys and payloads split at the same slot, either spare buffer may be missing.
-	u32 lo = (!env().no_aux_slots && cap1 >= (u32)C2::TILE && (kspare || vspare)) ? (u32)std::min<size_t>(n / cap1, 255) : 0u;
-	auto part_span = [&](const void *spare, const void *scratch, size_t esz) {   // both parts within 2^32 elements of the lower one?
-		const uintptr_t lo_a = (uintptr_t)spare, hi_a = (uintptr_t)scratch - (size_t)lo * cap1 * esz;
-		return (std::max(lo_a, hi_a) - std::min(lo_a, hi_a)) / esz + (size_t)257 * cap1 + C2::TILE;
-	};
-	for (int attempt = 0; attempt < 2; ++attempt) {
-		const u32 klo = kspare ? lo : 0u, vlo = vspare ? lo : 0u;
-		if (c.slack1.ensure(((size_t)(256 - klo) * cap1 + C2::TILE) * sizeof(KT)) != RSX_OK ||
-		    c.slack1_v.ensure(((size_t)(256 - vlo) * cap1 + C2::TILE) * sizeof(VT)) != RSX_OK)
-			break;   // (the test below sees it)
-		if (lo && ((klo && part_span(kspare, c.slack1.p, sizeof(KT)) >= ((uintptr_t)1 << 32)) ||
-		           (vlo && part_span(vspare, c.slack1_v.p, sizeof(VT)) >= ((uintptr_t)1 << 32)))) {
-			lo = 0;   // too far apart for 32-bit element offsets: all slots in scratch
-			continue;
-		}
-		break;
-	}
-	const u32 klo = kspare ? lo : 0u, vlo = vspare ? lo : 0u;
-	if (c.slack1.ensure(((size_t)(256 - klo) * cap1 + C2::TILE) * sizeof(KT)) != RSX_OK ||
-	    c.slack1_v.ensure(((size_t)(256 - vlo) * cap1 + C2::TILE) * sizeof(VT)) != RSX_OK ||
-	    c.slack.ensure(((size_t)65536 * cap2 + C2::TILE) * sizeof(K2)) != RSX_OK ||
-	    c.slack_v.ensure(((size_t)65536 * cap2 + C2::TILE) * sizeof(VT)) != RSX_OK) {
-		(void)hipGetLastError();   // (no room: as blind_enqueue -- what was allocated goes back, nobody asks again)
-		c.slack1_cap = c.slack_cap = 0;
-		if (!g_in_async) {
-			c.slack1.release();
-			c.slack1_v.release();
-			c.slack.release();
-			c.slack_v.release();
-			c.blind_no_room = true;
-		}
-		return RSX_OK;
-	}
-	RSX_TRY(seg_layout<KT>(c, n));   // (Sc2Cfg<KT, NoVal> and <KT, VT> have the same tile: 32 Ki elements)
-	static_assert((int)C2::TILE == (int)Sc2Cfg<KT, NoVal>::TILE, "one layout for both");
-	RSX_TRY(c.gscan.ensure(256 * sizeof(u64)));
-	const u64 ntiles0 = (n + C2::TILE - 1) / C2::TILE;
-	const u64 rows = ntiles0 + 256;
-	const size_t st_bytes = 256 + rows * 256 * 4;
-	SegCtl *ctl = (SegCtl *)c.seg.p;
-	SegTile *tiles = (SegTile *)((char *)c.seg.p + c.seg_tiles_off);
-	LeafSeg *segtab = (LeafSeg *)((char *)c.seg.p + c.seg_segtab_off);
-	u32 *btile = (u32 *)((char *)c.seg.p + c.seg_btile_off);
-	u64 *off1 = (u64 *)c.gscan.p;
-	if (!c.seg_ev)
-		HIP_TRY(hipEventCreateWithFlags(&c.seg_ev, hipEventDisableTiming));
-	c.host_segctl->mode = SEG_MODE_NONE;
-	RSX_TRY(blind_forget_device_backoff(c));
-	hipLaunchKernelGGL((rsx_blind_precheck_kernel<KT>), dim3(1 + 512), dim3(1024), 0, c.stream, kin, (u64)n, ka, ctl, c.plan(),
-	                   c.dev_host_plan, (u32x4 *)((char *)c.seg.p + c.seg_status_off), (u64)(2 * st_bytes / 16),
-	                   (u32)sizeof(KT),   // (every column kept: the callers' parity rule below counts on it)
-	                   0u, 0u,
-	                   // rank sorts (no keys wanted back): keys whose byte columns do not spread but whose VARYING bits would, packed
-	                   // together, go by those (SegCtl::compact, README.md:716-758)
-	                   (u32)((vin == nullptr && kfinal == nullptr && !env().no_packed_keys) ? 1 : 0), (u32)(g_in_async ? 1 : 0));
-	SegArgs sa{};
-	sa.ctl = ctl;
-	sa.hist = (const u32 *)((char *)c.seg.p + c.seg_hist_off);
-	sa.tiles = tiles;
-	sa.slots = (u32)sizeof(KT) - 1;
-	sa.overflow = &ctl->overflow;
-	char *base0 = (char *)c.seg.p + c.seg_status_off, *base1 = base0 + st_bytes;
-	// the two parts of the level-1 slots (SegArgs): one base per array for the level-1 pass's stores and the parts' offsets from it;
-	// for the level-2 pass the spare buffer as the array and the scratch part's virtual slot 0 as the other one
-	KT *k1out = (KT *)c.slack1.p, *k1lo = (KT *)c.slack1.p;
-	VT *v1out = (VT *)c.slack1_v.p, *v1lo = (VT *)c.slack1_v.p;
-	const void *k1hi = nullptr, *v1hi = nullptr;
-	sa.lo_slots = lo;
-	if (klo) {
-		const uintptr_t lo_a = (uintptr_t)kspare, hi_a = (uintptr_t)c.slack1.p - (size_t)lo * cap1 * sizeof(KT), base_a = std::min(lo_a, hi_a);
-		sa.out_off_lo = (u32)((lo_a - base_a) / sizeof(KT));
-		sa.out_off_hi = (u32)((hi_a - base_a) / sizeof(KT));
-		k1out = (KT *)base_a;
-		k1lo = kspare;
-		k1hi = (const void *)hi_a;
-	}
-	if (vlo) {
-		const uintptr_t lo_a = (uintptr_t)vspare, hi_a = (uintptr_t)c.slack1_v.p - (size_t)lo * cap1 * sizeof(VT), base_a = std::min(lo_a, hi_a);
-		sa.v_off_lo = (u32)((lo_a - base_a) / sizeof(VT));
-		sa.v_off_hi = (u32)((hi_a - base_a) / sizeof(VT));
-		v1out = (VT *)base_a;
-		v1lo = vspare;
-		v1hi = (const void *)hi_a;
-	}
-	{
-		ProfScope prof(1, (u64)n * (2 * sizeof(KT) + (vin ? 2 : 1) * sizeof(VT)), c.stream);
-		sa.slack_cap = cap1;
-		const u32 flags = (u32)SCATTER_SEG_SLACK | (u32)SCATTER_BLIND | (u32)SCATTER_BLIND_TOP | (vin ? 0u : (u32)SCATTER_GEN_INDEX);
-		hipLaunchKernelGGL((rsx_scatter2_kernel<KT, VT, u32, C2, false, DIG_GENERIC, false, KT, true>), dim3((unsigned)ntiles0),
-		                   dim3(C2::BLOCK), 0, c.stream, kin, k1out, vin, v1out, (u64)n, 0u,
-		                   (const u64 *)c.ghist(), 1u, (u32 *)(base1 + 256), (u32 *)base1, ka, flags, (u64 *)nullptr,
-		                   (const Plan *)c.plan(), 0u, 0u, (const u32 *)nullptr, sa);
-	}
-	sa.out_off_lo = sa.out_off_hi = sa.v_off_lo = sa.v_off_hi = 0;
-	sa.kin_hi = k1hi;
-	sa.vin_hi = v1hi;
-	hipLaunchKernelGGL(rsx_seg_tiles_kernel, dim3(32), dim3(256), 0, c.stream, (const u64 *)c.ghist(), (u64)n, (const Plan *)c.plan(),
-	                   (u32)C2::TILE, tiles, ctl, btile, off1, cap1, (const u32 *)(base1 + 256), (u32)ntiles0);
-	{
-		ProfScope prof(1, (u64)n * (sizeof(KT) + sizeof(K2) + 2 * sizeof(VT)), c.stream);
-		sa.slack_cap = cap2;
-		hipLaunchKernelGGL((rsx_scatter2_kernel<KT, VT, u32, C2, false, DIG_GENERIC, false, K2, true>), dim3((unsigned)rows),
-		                   dim3(C2::BLOCK), 0, c.stream, (const KT *)k1lo, (K2 *)c.slack.p, (const VT *)v1lo,
-		                   (VT *)c.slack_v.p, (u64)n, 0u, (const u64 *)c.ghist(), 1u, (u32 *)(base0 + 256), (u32 *)base0, ka,
-		                   (u32)SCATTER_SEG_SLACK | (u32)SCATTER_BLIND, (u64 *)nullptr, (const Plan *)c.plan(), 0u, 0u,
-		                   (const u32 *)nullptr, sa);
-	}
-	hipLaunchKernelGGL((rsx_seg_slack_plan_kernel<u32>), dim3(256), dim3(256), 0, c.stream, (const u32 *)(base0 + 256), (const u32 *)btile,
-	                   (const u64 *)c.ghist(), (const Plan *)c.plan(), ctl, segtab, cap2, c.dev_host_segctl, (const u64 *)off1,
-	                   1u | ((env().probe & 1u) << 8));
-	HIP_TRY(hipGetLastError());
-	HIP_TRY(hipEventRecord(c.seg_ev, c.stream));
-	{
-		ProfScope prof(2, (u64)n * (sizeof(K2) + 2 * sizeof(VT) + (kfinal ? sizeof(KT) : 0)), c.stream);
-		if (!env().no_leaf16) {
-			// the compounds (key half, position) through one placement and the register passes (rsx_leafp_kernel); what it
-			// leaves alone -- or everything, if the sample saw the keys' low bits cluster -- through the LDS passes of round 3
-			// Three shapes by the slots' capacity (the host knows it): a leaf's fixed costs -- cells zeroed and scanned, barriers
-			// of the whole workgroup -- follow the shape, not the pairs in it (16 Mi pairs through the 5120-pair shape: 0.48 ms
-			// for the leaves alone, as much as 128 Mi pairs take)
-			typedef LeafKCfg<512, 5120, 8> P5;
-			typedef LeafKCfg<256, 2560, 8, 11> P2;
-			typedef LeafKCfg<128, 1280, 6, 10> P1;
-			u32 *redo = (u32 *)((char *)c.seg.p + c.seg_redo_off);
-#define RSX_LEAFP(P) \
-	hipLaunchKernelGGL((rsx_leafp_kernel<KT, VT, P, true>), dim3(65536u), dim3(P::BLOCK), 0, c.stream, (const KT *)c.slack.p, \
-	                   (const VT *)c.slack_v.p, cap2, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab, ctl, ka, redo, \
-	                   (u32)env().leaf16_maxbin)
-			typedef LeafKCfg<64, 256, 8, 9> P0;    // slots of up to 256 pairs: a wave per leaf
-			typedef LeafKCfg<64, 512, 8, 10> P0b;  // ... and of 512 (arrays of 11.5 .. 27 Mi pairs)
-			if (big)
-				RSX_LEAFP(P10);
-			else if (cap2 <= (u32)P0::CAP && !env().no_leaf16q)
-				RSX_LEAFP(P0);
-			else if (cap2 <= (u32)P0b::CAP && !env().no_leaf16q)
-				RSX_LEAFP(P0b);
-			else if (cap2 <= (u32)P1::CAP)
-				RSX_LEAFP(P1);
-			else if (cap2 <= (u32)P2::CAP)
-				RSX_LEAFP(P2);
-			else
-				RSX_LEAFP(P5);
-#undef RSX_LEAFP
-			if (big)
-				hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, LB, true>), dim3(4096), dim3(LB::BLOCK), 0, c.stream, (const KT *)c.slack.p,
-				                   (const VT *)c.slack_v.p, cap2, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab,
-				                   (const SegCtl *)ctl, ka, (u32)HYB_TWO_LEVEL, (const u64 *)nullptr, (u64)0, (const u32 *)redo);
-			else
-				hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L, true>), dim3(4096), dim3(L::BLOCK), 0, c.stream, (const KT *)c.slack.p,
-				                   (const VT *)c.slack_v.p, cap2, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab,
-				                   (const SegCtl *)ctl, ka, (u32)HYB_TWO_LEVEL, (const u64 *)nullptr, (u64)0, (const u32 *)redo);
-		} else {
-			if (big)
-				hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, LB, true>), dim3(env().leaf_grid), dim3(LB::BLOCK), 0, c.stream, (const KT *)c.slack.p,
-				                   (const VT *)c.slack_v.p, cap2, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab,
-				                   (const SegCtl *)ctl, ka);
-			else
-				hipLaunchKernelGGL((rsx_leaf_pairs_kernel<KT, VT, L, true>), dim3(env().leaf_grid), dim3(L::BLOCK), 0, c.stream, (const KT *)c.slack.p,
-				                   (const VT *)c.slack_v.p, cap2, kfinal, vfinal, (const Plan *)c.plan(), (const LeafSeg *)segtab,
-				                   (const SegCtl *)ctl, ka);
-		}
-	}
-	HIP_TRY(hipGetLastError());
-	*enqueued = 1;
-	return RSX_OK;
-}
-
-// ... and the blocking sorts' use of it: the host waits for the verdict (the event lies behind the slack plan kernel, in front of
-// the leaves) and remembers an attempt that was called off (blind_called_off: back-off)
-template <typename KT, typename VT>
-int pairs_blind(Ctx &c, const KT *kin, const VT *vin, KT *kfinal, VT *vfinal, size_t n, KdfArgs<KT> ka, rsx_info *info, int *done,
-                KT *kspare = nullptr, VT *vspare = nullptr)
-{
-	*done = 0;
-	int enqueued = 0;
-	const size_t pmark = prof_mark();
-	RSX_TRY((pairs_blind_enqueue<KT, VT>(c, kin, vin, kfinal, vfinal, n, ka, &enqueued, kspare, vspare)));
-	if (!enqueued)
-		return RSX_OK;
-	HIP_TRY(hipEventSynchronize(c.seg_ev));
-	if (c.host_segctl->mode != SEG_MODE_LEAVES) {
-		blind_called_off(c, blind_kind<KT>(sizeof(VT), vin == nullptr));   // (no payloads given: a rank sort)
-		prof_called_off(pmark, c.stream);
-		return RSX_OK;
-	}
-	c.blind_backoff[blind_kind<KT>(sizeof(VT), vin == nullptr)] = 0;
-	info_from_plan(info, *c.host_plan);
-	if (info)
-		info->hybrid = 5u;
-	*done = 1;
 	return RSX_OK;
 }
 
@@ -2447,13 +964,8 @@ int sort_pairs_device_impl(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int
 	RSX_TRY(plan_phase<KT>(c, k0, n, ka, &plan, 0, (c.fast && !capture_armed() && !verify_mode()) ? hybrid_caps_pairs<KT>(n, sizeof(VT), true) : HybCaps{0, 0, 0, 0}));
 	info_from_plan(info, plan);
 	RSX_TRY(capture_hist(c, n, sizeof(KT)));
-	if (plan.sorted) {
-		if (info) {
-			info->early_exit = 2;
-			info->ncols = 0;
-		}
-		return RSX_OK;
-	}
+	if (plan.sorted)
+		return finish_sorted(info);
 	if constexpr (sizeof(KT) == 4 && sizeof(VT) == 4) {
 		if (plan.hyb == HYB_ONE_LEVEL) {
 			// one MSB pass and the pairs' leaves (mid-size arrays)
@@ -2654,12 +1166,7 @@ int sort_rank_device_impl(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, in
 	if (plan.sorted) {                       // radix_sort_rank.hpp:52,:55-57: first half = iota
 		hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, ib, (u64)n);
 		HIP_TRY(hipGetLastError());
-		if (info) {
-			info->early_exit = 2;
-			info->ncols = 0;
-		}
-		*result = ib;
-		return RSX_OK;
+		return finish_sorted(info, result, ib);
 	}
 	const u32 P = plan.ncols;
 	// README.md:716-758, "key compaction" (SURVEY.md 8 f4), behind RSX_COMPACT_BITS=1: when the bits that vary among the
@@ -2802,8 +1309,8 @@ int sort_rank_inplace_async(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, 
 			RSX_TRY((pairs_blind_enqueue<KT, IT>(c, src, (const IT *)nullptr, (KT *)nullptr, ib, n, ka, &blind, (KT *)(ib + n), ib)));
 	}
 	if (blind)
-		pverdict.attempt_enqueued((const SegCtl *)c.seg.p);
-	c.pass_gate = blind ? (const SegCtl *)c.seg.p : nullptr;
+		pverdict.attempt_enqueued(SegView(c).ctl());
+	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
 	c.async_tried_blind = blind != 0;
 	int rc = plan_phase<KT>(c, src, n, ka, nullptr, status_total);
 	c.pass_alt = c.keys[1].p;

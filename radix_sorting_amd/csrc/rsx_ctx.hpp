@@ -1,5 +1,5 @@
 // rsx_ctx.hpp: what every host function uses -- the error convention (fail, HIP_TRY, RSX_TRY), DevBuf, the per (device, stream) context
-// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp, ahead of the routes.
+// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp and rsx_seg_layout.hpp, ahead of the routes.
 #pragma once
 
 namespace {
@@ -174,7 +174,7 @@ struct Ctx {
 	DevBuf ckeys;       // rank sorts: the keys' varying bits packed together (RSX_COMPACT_BITS)
 	DevBuf joint;       // 2-byte keys: [65536 u32 counts][65537 u64 offsets] of the 16-bit digit (rsx_joint16_kernel)
 	DevBuf seg;         // two-level sorts (rsx_hybrid.hpp): [SegCtl][per-bucket digit counts][status regions][leaf segments][tiles]
-	size_t seg_hist_off = 0, seg_status_off = 0, seg_segtab_off = 0, seg_tiles_off = 0, seg_btile_off = 0, seg_redo_off = 0;
+	SegLayout seg_lay;  // ... where they lie, for the sort being enqueued (seg_layout, rsx_route_levels.hpp; read through SegView)
 	SelfPlanArgs pass_sp{nullptr, nullptr, nullptr, nullptr, HybCaps{0, 0, 0, 0}};   // a self-planned pass 0 (SCATTER_SELF_PLAN)
 	DevBuf gscan;       // [256] u64: the highest kept column's offsets from a self-planned pass 0 (for the leaves)
 	// rsx_sort_inplace_async after an attempt without the histogram: the control block whose `mode` tells the histogram-first

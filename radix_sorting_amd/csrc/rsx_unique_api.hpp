@@ -11,8 +11,7 @@ template <typename KT> bool unique_sample_wanted(const Ctx &c, size_t n)
 {
 	if constexpr (sizeof(KT) < 4)
 		return false;
-	if (env().no_blind || env().no_slack || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() || c.small.external ||
-	    env().no_speculation)
+	if (!blind_gate(c))
 		return false;
 	if (n < ((size_t)1 << 22) || n >= blind_keys_end<KT>())
 		return false;

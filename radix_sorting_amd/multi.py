@@ -131,7 +131,7 @@ def bins_are_even(counts, levels):
     """May the local sort of the received bins `counts` (global counts, exact) be told RSX_HINT_EVEN_TOP_DIGITS?
 
     The hint switches off the level-1 test of the sample of a sort without a histogram, and that sort's level-1 slots hold 1.25
-    times the mean (slot_cap_for in csrc/rsx.hip): a bin above that loses the attempt after a full pass, for certain.  So: no bin
+    times the mean (slot_cap_for in csrc/rsx_route_levels.hpp): a bin above that loses the attempt after a full pass, for certain.  So: no bin
     above EVEN_FACTOR = 1.2 means, at least two bins, and nothing refined (`levels` = 0: refined bins are not digits of one byte)."""
     c = np.asarray(counts, dtype=np.float64)
     return bool(levels == 0 and c.size >= 2 and float(c.max()) <= EVEN_FACTOR * float(c.mean()))

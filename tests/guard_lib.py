@@ -10,7 +10,7 @@ fills both guards with a seeded splitmix64 pattern (its own seed, so that a stra
 out a typed view of the buffer that starts at a chosen residue mod 256, and `check()` compares both guards with the copies kept
 when they were filled.
 
-Also here: the slot geometry of the sort without a histogram restated from radix_sorting_amd/csrc/rsx.hip (slot_cap_for,
+Also here: the slot geometry of the sort without a histogram restated from radix_sorting_amd/csrc/rsx_route_levels.hpp (slot_cap_for,
 level1_slot_cap, blind_enqueue's `lo`, the condition of the 8-byte narrow level-1 form), so that a test can size its guards
 above the largest overrun a wrong slot could make before anything is launched.
 """
@@ -127,17 +127,17 @@ def check_all(*pairs):
         raise GuardDamage("\n".join(msgs))
 
 
-# ---- the slot geometry of a sort without a histogram (rsx.hip), restated ---------------------------------------------------
+# ---- the slot geometry of a sort without a histogram (rsx_route_levels.hpp), restated ---------------------------------------------------
 
 def slot_cap_for(mean):
-    """rsx.hip slot_cap_for: 1.25 x the mean and at least mean + 7 standard deviations + 8, rounded up to 256 keys."""
+    """rsx_route_levels.hpp slot_cap_for: 1.25 x the mean and at least mean + 7 standard deviations + 8, rounded up to 256 keys."""
     r = math.isqrt(mean)
     need = max(mean + mean // 4, mean + 7 * (r + 1) + 8)
     return (need + 255) // 256 * 256
 
 
 def level1_slot_cap(mean, ksize, pad_kib=0, odd_stride=True):
-    """rsx.hip level1_slot_cap<KT>: slots of a MiB and more an odd number of 64 KiB apart; RSX_CAP1_PAD_KIB adds pad_kib KiB."""
+    """rsx_route_levels.hpp level1_slot_cap<KT>: slots of a MiB and more an odd number of 64 KiB apart; RSX_CAP1_PAD_KIB adds pad_kib KiB."""
     cap1 = slot_cap_for(mean) + pad_kib * (1024 // ksize)
     if odd_stride and cap1 * ksize >= (1 << 20):
         unit = 65536 // ksize

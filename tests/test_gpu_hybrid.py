@@ -537,3 +537,35 @@ def test_blind_no_shift_switch(blind_on):
     assert check(a, ol.U32, ol.ASC, None, "shifted").hybrid == 5
     blind_on.setenv("RSX_NO_SHIFT", "1")
     assert check(a, ol.U32, ol.ASC, None, "RSX_NO_SHIFT=1").hybrid != 5
+
+
+def test_routes_interleaved_in_one_context_share_the_control_block(monkeypatch):
+    """The counted (key, payload) route, the counted keys-only route and the sorts without a histogram lay out the same control
+    block (seg_layout) and leave its offsets in the context: six sorts on one stream, each route after another one's layout
+    -- and after another key size's --, every result bit for bit the oracle's and every route the one named (a silent
+    fallback to one pass per column fails)."""
+    monkeypatch.setenv("RSX_NO_SLACK", "1")      # (RSX_NO_BLIND=1 and RSX_TWO_LEVEL_MIN_LOG2=22: the module's fixture)
+    np_, nk, n64 = (1 << 22) + 5, (1 << 23) + 12345, (1 << 23) + 7
+    pa = ol.splitmix_fill(np_, ol.U32, 4101, 0xFFFFFFFF).view(np.uint32)
+    perm = ol.stable_argsort_by_kdf(pa, ol.U32)
+    ka = ol.splitmix_fill(nk, ol.U32, 4102, 0xFFFFFFFF)
+    a64 = ol.splitmix_fill(n64, ol.U64, 4103, (1 << 64) - 1)
+
+    def pairs(want_hybrid, step):
+        keys = _dev(pa)
+        vals = torch.arange(np_, dtype=torch.int32, device="cuda") * 3 + 1      # (u32 payloads that are not the position)
+        k, v, info = rsa.radix_sort_pairs(keys, torch.zeros_like(keys), vals, torch.zeros_like(vals), dtype=ol.U32)
+        torch.cuda.synchronize()
+        assert info.hybrid == want_hybrid, (step, info.hybrid)
+        assert np.array_equal(k.cpu().numpy().view(np.uint32), pa[perm]), step
+        assert np.array_equal(v.cpu().numpy().astype(np.int64), perm.astype(np.int64) * 3 + 1), step
+
+    pairs(2, 1)                                   # 1: the counted pairs route
+    check(ka, ol.U32, ol.ASC, 2, "step 2")        # 2: the counted keys-only route
+    pairs(2, 3)                                   # 3: the pairs again, behind the keys-only layout
+    monkeypatch.delenv("RSX_NO_BLIND")
+    monkeypatch.delenv("RSX_NO_SLACK")
+    rsa.reload_env()
+    pairs(5, 4)                                   # 4: the pairs without a histogram
+    check(ka, ol.U32, ol.ASC, 5, "step 5")        # 5: keys only without a histogram
+    check(a64, ol.U64, ol.ASC, 5, "step 6")       # 6: 8-byte keys: another layout in the same block

@@ -1,5 +1,5 @@
 """CPU checks of tests/guard_lib.py: the guard bands catch a write one byte before and one byte after the buffer, report where,
-and the restated slot geometry gives the numbers rsx.hip's comments and tests/test_gpu_bounds.py rely on.  No GPU: the helper
+and the restated slot geometry gives the numbers rsx_route_levels.hpp's comments and tests/test_gpu_bounds.py rely on.  No GPU: the helper
 runs on CPU tensors here (the same layout and comparison as on the device)."""
 import numpy as np
 import pytest

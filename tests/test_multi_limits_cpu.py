@@ -350,7 +350,7 @@ def test_default_limits_leave_small_inputs_to_all_to_all_single(tmp_path, name):
 # ---- the even-digits hint -----------------------------------------------------------------------------------------------------
 
 def slot_cap(mean):
-    """slot_cap_for of csrc/rsx.hip: the keys a level-1 slot holds when the mean bucket has `mean` keys -- 1.25 times the mean, at
+    """slot_cap_for of csrc/rsx_route_levels.hpp: the keys a level-1 slot holds when the mean bucket has `mean` keys -- 1.25 times the mean, at
     least seven standard deviations of an even spread above it, rounded up to 256."""
     r = int(np.floor(np.sqrt(mean)))
     while (r + 1) * (r + 1) <= mean:
