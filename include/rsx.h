@@ -121,7 +121,8 @@
  *   RSX_PROBE=bits          (measurements; results stay right) 1: the leaf table in reverse slot order, 4: every device-scheduled
  *                           sort as if called through rsx_sort_inplace_async_hint;
  *   RSX_NO_SLACK=1, RSX_TWO_LEVEL_MIN_LOG2=k, RSX_NO_SELF_PLAN=1, RSX_NO_FUSED_HIST=1
- *                           parts of the other routes.
+ *                           parts of the other routes; RSX_NO_FUSED_HIST=1 (the histogram and the plan
+ *                           as two launches) is exercised by tests/test_gpu_decisions.py.
  *   RSX_NO_SMALL_SORT, RSX_NO_HOST_SMALL, RSX_NO_FILL_RUNS, RSX_NO_SMALL_TILES, RSX_NO_SPECULATION,
  *   RSX_NO_NARROW_KEYS
  *                           switch single optimisations off (tests).

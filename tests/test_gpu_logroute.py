@@ -7,12 +7,15 @@ rs_sort_main (radix_sort.hpp:31-93) and compared with the device's result bit fo
 it the cases the route must get right or must leave alone: odd lengths, constant bits above the varying ones, signed keys,
 a pre-sorted array (the early exit, aux untouched), keys that cluster in their mantissa bits (a level-2 slot overflows: the
 attempt is lost and the ordinary path sorts the untouched input), keys up to 2^44 (taken) and 2^45 (refused), descending order.
+The route's two decisions at their edges -- a sorted array with ONE descent at every seam of rsx_log_hist_kernel, one key with a
+bit above the window -- are in tests/test_gpu_decisions.py (family D), which shares the generator below (tests/decide_lib.py).
 """
 import numpy as np
 import pytest
 
 import oracle_lib as ol
 import radix_sorting_amd as rsa
+from decide_lib import zipf_like
 
 pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
@@ -30,14 +33,6 @@ def _fresh_routes():
     rsa.reload_env()
     yield
     torch.cuda.empty_cache()
-
-
-def zipf_like(n, seed, bmax=40):
-    """SURVEY.md 8d cfg 3 (iv), integer-only: identical bits on host and device."""
-    r = ol.splitmix_fill(n, ol.U64, seed)
-    b = np.uint64(1) + ((r >> np.uint64(58)) % np.uint64(bmax))
-    one = np.uint64(1)
-    return (one << (b - one)) + (r & ((one << (b - one)) - one))
 
 
 def _sort(a, dt, order=rsa.ASCENDING):
