@@ -17,7 +17,7 @@ oracle: lib
 	$(MAKE) -C oracle
 
 # C++ check of the template surface in include/ (needs a GPU to run: tests/test_gpu_cpp.py)
-cpp: tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check
+cpp: tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/rankdata_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check
 
 tests/cpp/dropin_check: tests/cpp/dropin_check.cpp include/radix_sort.hpp include/radix_sort_rank.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
 	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/dropin_check.cpp -Lradix_sorting_amd -lrsx \
@@ -29,6 +29,10 @@ tests/cpp/unique_check: tests/cpp/unique_check.cpp include/radix_sort.hpp includ
 
 tests/cpp/group_check: tests/cpp/group_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
 	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/group_check.cpp -Lradix_sorting_amd -lrsx \
+	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
+
+tests/cpp/rankdata_check: tests/cpp/rankdata_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
+	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/rankdata_check.cpp -Lradix_sorting_amd -lrsx \
 	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
 
 tests/cpp/topk_check: tests/cpp/topk_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
@@ -63,7 +67,7 @@ tools/radix_bench: tools/radix_bench.cpp include/radix_sort.hpp include/radix_so
 	-L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../radix_sorting_amd' -Wl,-rpath,/opt/rocm/lib -o $@
 
 clean:
-	rm -f radix_sorting_amd/librsx.so tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check tools/radix tools/radix_bench
+	rm -f radix_sorting_amd/librsx.so tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/rankdata_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check tools/radix tools/radix_bench
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle cpp cli clean

@@ -317,6 +317,29 @@ size_t radix_sort_group(const T *src, IdxType *inverse, size_t n, T *keys = null
 	return n_groups;
 }
 
+// Not in the reference's header (its README's counting sort read per key): for every element of src, which is not written,
+// where it stands in the stable sorted order by kf(element) into place -- the inverse of radix_sort_rank's permutation, what
+// argsort(argsort(x)) returns -- and, if given, how many elements have a smaller derived key into less and how many an equal
+// one (itself included) into equal; room for n each, any of the three may be nullptr but not all.  All 0-based: the tie
+// methods of a ranking are ordinal = place, min = less, max = less + equal - 1, average = less + (equal - 1) / 2
+// (rsx_sort_rankdata).  Scalar T with basic_kdfs::kdf or rsx_kdf::descending<T>.
+template <typename T, typename IdxType = uint32_t, typename KeyFunc = decltype(basic_kdfs::kdf<T>)>
+void radix_sort_rankdata(const T *src, size_t n, IdxType *place, IdxType *less = nullptr, IdxType *equal = nullptr,
+                         KeyFunc &&kf = basic_kdfs::kdf<T>)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, KeyFunc> || rsx_detail::is_descending_kdf_v<T, KeyFunc>,
+	              "radix_sort_rankdata takes scalar keys with basic_kdfs::kdf or rsx_kdf::descending");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_rankdata: IdxType of 4 or 8 bytes");
+	if constexpr (rsx_detail::may_be_default_kdf_v<T, KeyFunc>)
+		if (!rsx_detail::kdf_kind<T, KeyFunc>::is_default(kf))
+			throw std::invalid_argument("radix_sort_rankdata: a function other than basic_kdfs::kdf<T> was passed as KeyFunc");
+	const int rc = rsx_sort_rankdata(src, n, rsx_detail::dtype_of<T>(),
+	                                 rsx_detail::is_descending_kdf_v<T, KeyFunc> ? RSX_DESCENDING : RSX_ASCENDING, place, less, equal,
+	                                 sizeof(IdxType), nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_rankdata", rc);
+}
+
 // Not in the reference's header (its README's "Hybrids" note): the first k elements of the stable sorted order of src, which
 // is not written, into out (room for k), and their positions in src into idx if given (room for k; equal keys in ascending
 // index order, as radix_sort_rank orders them).  Returns k.  Scalar T with basic_kdfs::kdf; RSX_DESCENDING for the

@@ -132,6 +132,8 @@
  *   RSX_GROUP_MAX_BITS=k    rsx_sort_group*: the widest bitmap under the rank cells is 2^k bits (default 24, at most 30); 0: never
  *                           a bitmap, cells or a count table -- everything but all-equal keys goes through the sort and the
  *                           heads pass (tests force that route with it, tools/group_probe.py sweeps the cut-off);
+ *   RSX_RANKDATA_NO_TABLES=1  rsx_sort_rankdata*: never a column table or a count table -- everything but all-equal keys goes
+ *                           through the sort and the runs pass (tests force that route with it, tools/rankdata_probe.py times it);
  *   RSX_TOPK_FORCE=1        rsx_sort_topk*: the select route whenever n >= 2 and 0 < k <= n; =2: always the sort route
  *                           (tests run both and compare; tools/topk_probe.py times both);
  *   RSX_NTH_FORCE=1         rsx_sort_nth*: the select route whenever n >= 2 and 1 <= distinct ranks <= RSX_NTH_MAX_SELECT_RANKS;
@@ -417,6 +419,55 @@ int rsx_sort_group_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_orde
 int rsx_sort_group(const void *src, size_t n, rsx_dtype dtype, rsx_order order,
                    void *out_inverse, void *out_keys, void *out_counts, void *out_first,
                    size_t idx_bytes, size_t *n_groups, rsx_group_info *info);
+
+/* ---- every element's place in the sorted order: the inverse of rsx_sort_rank (a counting sort's prefix sums, read per key) -- */
+
+/* For every element where it stands in the stable sorted order, and how many elements are smaller than / equal to it.
+ * Let R[0 .. n) be what rsx_sort_rank returns for the same keys, dtype and order: a stable argsort by kdf(key)
+ * (RSX_DESCENDING: by the complemented KDF).  All three outputs are 0-based; for every i < n:
+ *   - out_place[i] is the j with R[j] == i (the inverse permutation): the number of elements with a smaller derived key plus
+ *     the number of bit-equal elements at a lower index;
+ *   - out_less[i] is the number of elements whose derived key is below element i's, out_equal[i] the number whose derived key
+ *     equals it, itself included (rsx_sort_nth's n_less / n_equal): less[i] <= place[i] < less[i] + equal[i].
+ *   The tie methods of a ranking follow: ordinal = place, min = less, max = less + equal - 1, average = less + (equal - 1) / 2;
+ *   dense is rsx_sort_group's inverse.  Keys are bit patterns: -0.0 and +0.0 are different keys, NaNs with different payloads too.
+ *   - Buffers: d_src is never written.  Each output may be NULL, but not all three.  Each output has room for exactly n entries
+ *     of idx_bytes (4 or 8) and nothing outside [0, n) of any of them is touched; with 4, n must fit, or the call fails with
+ *     RSX_EINVAL "does not fit".
+ *   - Errors: bad dtype, order or idx_bytes, all outputs NULL, n && !src: RSX_EINVAL.  n == 0: RSX_OK, nothing written, no
+ *     device needed.  n == 1: it writes (0, 0, 1); rsx_sort_rankdata on host pointers needs no device for it,
+ *     rsx_sort_rankdata_device only for the stores.  Otherwise, without a GPU: RSX_ENODEVICE, nothing written.  A capturing
+ *     stream: RSX_EINVAL (the call waits for the plan of the keys).  A failed allocation of a table is not an error: the call
+ *     takes the sort route.
+ *   - Blocking: the call waits for what it has to read of the keys to choose the route (as rsx_sort_group_device); the device
+ *     outputs are valid for work ordered after it on `stream`.
+ * The route is chosen from what the call can observe of the keys (rsx_rankdata_info.route).  Where one byte
+ * column varies (all 1-byte keys) its 256 exclusive offsets, which the plan's histogram holds already, are less and equal of
+ * every key, and the place is the address a stable counting sort's scatter would compute, kept instead of used: three
+ * ordinary launches (counts per workgroup, their scan, the walk) and no sort.  Where the place is not wanted and at most 16 bits
+ * vary in keys of 2 bytes or more, the counts of the packed varying bits are made in LDS (rsx_sort's 16-bit digit), scanned and
+ * looked up.  Everything else is a stable key + index sort of a workspace copy (rsx_sort_pairs_device's routes; none where
+ * the input is sorted already), then the permutation inverted, or the heads pass and one pass over the runs.
+ * Memory, in the (device, stream) context: a table of at most 2 MiB, or a copy of the keys, its second buffer and 2 n indices;
+ * freed by rsx_release / rsx_release_stream. */
+enum { RSX_RANKDATA_TRIVIAL = 0,   /* n < 2, or every key equal                                          */
+       RSX_RANKDATA_TABLE = 1,     /* one kept column: lookups in its 256 offsets, the place by counting */
+       RSX_RANKDATA_COUNT16 = 2,   /* at most 16 varying bits, no place: count table in LDS, scan, lookup */
+       RSX_RANKDATA_SORT = 3 };    /* stable key + index sort (any route), inverse scatter or runs pass  */
+typedef struct rsx_rankdata_info {
+	rsx_info sort;          /* as rsx_unique_info.sort */
+	uint32_t route;         /* RSX_RANKDATA_* */
+	uint32_t varying_bits;  /* popcount of the KDF bits that differ among the keys; 0 = not computed */
+	uint64_t table_bytes;   /* offsets, bases or counts used, 0 otherwise */
+} rsx_rankdata_info;
+
+int rsx_sort_rankdata_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_order order,
+                             void *d_out_place, void *d_out_less, void *d_out_equal,
+                             size_t idx_bytes, void *stream, rsx_rankdata_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind) */
+int rsx_sort_rankdata(const void *src, size_t n, rsx_dtype dtype, rsx_order order,
+                      void *out_place, void *out_less, void *out_equal,
+                      size_t idx_bytes, rsx_rankdata_info *info);
 
 /* ---- the first k of the sorted order ("Hybrids", README.md:647-650: one MSB pass, then only the sub-result that matters) -- */
 

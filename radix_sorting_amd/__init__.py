@@ -66,6 +66,15 @@ class GroupInfo(C.Structure):
     _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
 
 
+# rsx_rankdata_info.route
+RANKDATA_TRIVIAL, RANKDATA_TABLE, RANKDATA_COUNT16, RANKDATA_SORT = range(4)
+
+
+class RankdataInfo(C.Structure):
+    """rsx_rankdata_info: the route rsx_sort_rankdata* took and what the front half of the sort decided."""
+    _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
+
+
 # rsx_topk_info.route
 TOPK_TRIVIAL, TOPK_SELECT, TOPK_SORT = range(3)
 
@@ -116,6 +125,7 @@ _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
 _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 _PTINFO = C.POINTER(TopkInfo)
 _PGINFO = C.POINTER(GroupInfo)
+_PRINFO = C.POINTER(RankdataInfo)
 _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 ABI = [
@@ -141,6 +151,8 @@ ABI = [
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_group_device", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP, _PSZ, _PGINFO]),
     ("rsx_sort_group", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _PSZ, _PGINFO]),
+    ("rsx_sort_rankdata_device", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _VP, _PRINFO]),
+    ("rsx_sort_rankdata", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _PRINFO]),
     ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
     ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
     ("rsx_sort_nth_device", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _VP, _PNINFO]),
@@ -373,6 +385,70 @@ def radix_sort_group(src, dtype=None, order=ASCENDING, idx_dtype=None, keys=Fals
     g = ng.value
     cut = lambda t: None if t is None else t[:g]
     return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
+
+
+def radix_sort_rankdata(src, dtype=None, order=ASCENDING, idx_dtype=None, place=True, less=False, equal=False, stream=None):
+    """rsx_sort_rankdata_device: for every key of ``src`` (not written) where it stands in the stable sorted order by kdf(key)
+    -- ``place``, the inverse of radix_sort_rank's permutation --, how many keys are smaller (``less``) and how many are equal
+    to it, itself included (``equal``), by BIT PATTERN (-0.0 and +0.0 are two keys).  All 0-based.
+
+    Returns (place, less, equal, info), None for what was not asked for.  ``place`` / ``less`` / ``equal``: True allocates the
+    output (n elements of ``idx_dtype``, default torch.int32), False leaves it out, a device tensor of exactly the room for n
+    elements or more is written in place; at least one must be wanted.  Asking for the place gives up the count table of up
+    to 16 varying bits (one varying byte column keeps its sort-free route)."""
+    import torch
+    _check_dev(src)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    n = src.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+
+    def buf(want, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(n, dtype=idx_dtype, device=src.device)
+        _check_dev(want)
+        if want.numel() < n or want.element_size() != idx_bytes:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    pl, le, eq = buf(place, "place"), buf(less, "less"), buf(equal, "equal")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    info = RankdataInfo()
+    check(lib().rsx_sort_rankdata_device(src.data_ptr(), n, code, order, ptr(pl), ptr(le), ptr(eq), idx_bytes, _stream_ptr(stream),
+                                         C.byref(info)))
+    cut = lambda t: None if t is None else t[:n]
+    return cut(pl), cut(le), cut(eq), info
+
+
+RANKDATA_METHODS = ("ordinal", "min", "max", "average", "dense")
+
+
+def rankdata(src, method="ordinal", dtype=None, order=ASCENDING, idx_dtype=None, stream=None):
+    """The rank of every key of ``src`` among all of them, as ``scipy.stats.rankdata`` assigns it -- but 0-BASED where scipy's
+    ranks are 1-based (add 1 for scipy's), and by bit pattern of the keys.  ``method``: "ordinal" (ties in index order: the
+    place of radix_sort_rankdata), "min" (less), "max" (less + equal - 1), "average" (less + (equal - 1) / 2, a float64
+    tensor) or "dense" (radix_sort_group's inverse).  Only the arrays the method needs are asked for, so "min" and "max" take
+    the table routes where they apply.  Returns (ranks, info)."""
+    if method not in RANKDATA_METHODS:
+        raise RsxError("rankdata: method %r is none of %s" % (method, ", ".join(RANKDATA_METHODS)))
+    if method == "dense":
+        inv, _, _, _, info = radix_sort_group(src, dtype=dtype, order=order, idx_dtype=idx_dtype, stream=stream)
+        return inv, info
+    if method == "ordinal":
+        pl, _, _, info = radix_sort_rankdata(src, dtype, order, idx_dtype, place=True, stream=stream)
+        return pl, info
+    if method == "min":
+        _, le, _, info = radix_sort_rankdata(src, dtype, order, idx_dtype, place=False, less=True, stream=stream)
+        return le, info
+    _, le, eq, info = radix_sort_rankdata(src, dtype, order, idx_dtype, place=False, less=True, equal=True, stream=stream)
+    if method == "max":
+        return le + eq - 1, info
+    import torch
+    return le.to(torch.float64) + (eq.to(torch.float64) - 1.0) / 2.0, info
 
 
 def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
@@ -720,6 +796,32 @@ def radix_sort_group_host(src, dtype, order=ASCENDING, idx_dtype=None, keys=Fals
     g = ng.value
     cut = lambda a: None if a is None else a[:g]
     return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
+
+
+def radix_sort_rankdata_host(src, dtype, order=ASCENDING, idx_dtype=None, place=True, less=False, equal=False):
+    """rsx_sort_rankdata on a host numpy buffer; returns (place, less, equal, info) as radix_sort_rankdata does (``idx_dtype``:
+    a 4- or 8-byte numpy integer type, default uint32; an output may also be given as a numpy array with room for n elements)."""
+    import numpy as np
+    if src.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src does not match the key type")
+    n = src.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+
+    def buf(want, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(n, dtype=idx_dtype)
+        if want.size < n or want.itemsize != idx_dtype.itemsize:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    pl, le, eq = buf(place, "place"), buf(less, "less"), buf(equal, "equal")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    info = RankdataInfo()
+    check(lib().rsx_sort_rankdata(src.ctypes.data, n, dtype, order, ptr(pl), ptr(le), ptr(eq), idx_dtype.itemsize, C.byref(info)))
+    cut = lambda a: None if a is None else a[:n]
+    return cut(pl), cut(le), cut(eq), info
 
 
 def radix_sort_topk_host(src, k, dtype, order=ASCENDING, want_idx=True, idx_dtype=None):

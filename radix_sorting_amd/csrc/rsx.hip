@@ -19,6 +19,7 @@
 #include "rsx_pass64.hpp"
 #include "rsx_unique.hpp"
 #include "rsx_group.hpp"
+#include "rsx_rankdata.hpp"
 #include "rsx_topk.hpp"
 #include "rsx_nth.hpp"
 #include "rsx_lex.hpp"
@@ -1933,6 +1934,7 @@ int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype
 // one file per feature: its host driver (anonymous namespace) and its entry points (extern "C")
 #include "rsx_unique_api.hpp"    // rsx_sort_unique[_device]
 #include "rsx_group_api.hpp"     // rsx_sort_group[_device]
+#include "rsx_rankdata_api.hpp"  // rsx_sort_rankdata[_device]
 #include "rsx_topk_api.hpp"      // rsx_sort_topk[_device]
 #include "rsx_nth_api.hpp"       // rsx_sort_nth[_device]
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]

@@ -200,6 +200,8 @@ struct Ctx {
 	DevBuf urecs;       // ... [8 u64: sample / totals][UniqueRec per chunk of the bitmap or tile of the sorted array]
 	DevBuf gcells;      // rsx_sort_group*: one GroupCell per word of the bitmap in ubits: the word and the set bits below it
 	DevBuf gout;        // ... rsx_sort_group on host buffers: the staged outputs
+	DevBuf rdtab;       // rsx_sort_rankdata*: [workgroups][256] u64 bases of the place, or [65536 u32 counts][65537 u64 offsets] of the packed varying bits
+	DevBuf rdout;       // ... rsx_sort_rankdata on host buffers: the staged outputs
 	DevBuf tkctl;       // rsx_sort_topk*: [TopkCtl][rows of the input's ranges][rows of the candidates'][their offsets]
 	DevBuf tkpairs;     // ... the k (key, index) pairs and the second buffers of their sort: [keys k][keys k][indices k][indices k]
 	DevBuf tkcand;      // ... the selected bucket's (key, index) candidates: [keys cap][indices cap], cap = n / 8 + 1024
@@ -309,6 +311,8 @@ struct Ctx {
 		urecs.release();
 		gcells.release();
 		gout.release();
+		rdtab.release();
+		rdout.release();
 		tkctl.release();
 		tkpairs.release();
 		tkcand.release();

@@ -75,6 +75,7 @@ struct Env {
 	unsigned log_min_log2 = 0;       // RSX_LOG_MIN_LOG2: ... from 2^this keys on (tests: 20; default: from 24 Mi keys)
 	unsigned unique_max_bits = UNIQUE_MAX_BITS_DEFAULT;   // RSX_UNIQUE_MAX_BITS=k: rsx_sort_unique*: the widest bitmap is 2^k bits (0: never a bitmap or a table; at most 30)
 	unsigned group_max_bits = GROUP_MAX_BITS_DEFAULT;     // RSX_GROUP_MAX_BITS=k: rsx_sort_group*: the widest bitmap under the rank cells is 2^k bits (0: never a bitmap, cells or a table; at most 30)
+	bool rankdata_no_tables = false; // RSX_RANKDATA_NO_TABLES=1 (tests, probe): rsx_sort_rankdata* always takes the sort route (no column table, no count table)
 	unsigned nth_force = 0;          // RSX_NTH_FORCE=1: rsx_sort_nth* selects whenever n >= 2 and 1 <= distinct ranks <= 64; =2: always the sort route
 	unsigned topk_force = 0;         // RSX_TOPK_FORCE=1: rsx_sort_topk* selects whenever n >= 2 and 0 < k <= n; =2: always the sort route
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
@@ -158,6 +159,7 @@ struct Env {
 		log_leaf_big = is_one("RSX_LOG_LEAF_BIG");
 		pairs_leaf_big = is_one("RSX_PAIRS_LEAF_BIG");
 		number("RSX_LOG_MIN_LOG2", &log_min_log2, 20, 29);
+		rankdata_no_tables = is_one("RSX_RANKDATA_NO_TABLES");
 		topk_force = one_or_two("RSX_TOPK_FORCE");
 		nth_force = one_or_two("RSX_NTH_FORCE");
 		within("RSX_LEX_PACK_BYTES", &lex_pack_bytes, 1, 8);

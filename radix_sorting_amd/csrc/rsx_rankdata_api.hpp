@@ -1,0 +1,316 @@
+// rsx_rankdata_api.hpp: rsx_sort_rankdata[_device] -- the host driver (routes by one column's offsets, the count table of the packed
+// varying bits or sort + runs over the kernels of rsx_rankdata.hpp, rsx_group.hpp and rsx_unique.hpp) and its entry points; part of
+// librsx.so's host side, included by rsx.hip behind rsx_group_api.hpp.
+#pragma once
+
+namespace {
+
+// ---- rsx_sort_rankdata_device: every element's place in the sorted order (rsx_rankdata.hpp) ---------------------
+// what the call writes: each may be nullptr
+template <typename IT> struct RankdataOut {
+	IT *place;
+	IT *less;
+	IT *equal;
+};
+
+enum : size_t { RANKDATA_TAB16_BYTES = 65536 * sizeof(u32) + 65537 * sizeof(u64) };
+
+// route 1, the place: three ordinary launches over one kept column.  *done = 0: no room for the table.
+template <typename KT, typename IT>
+int rankdata_place(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, u32 col, IT *place, rsx_rankdata_info *info, int *done)
+{
+	*done = 0;
+	const u64 per = ((u64)n + RANKDATA_PLACE_MAX_WGS - 1) / RANKDATA_PLACE_MAX_WGS;
+	const u64 share = (per + RANKDATA_PLACE_TILE - 1) / RANKDATA_PLACE_TILE * RANKDATA_PLACE_TILE;
+	const u32 wgs = (u32)(((u64)n + share - 1) / share);
+	const size_t bytes = (size_t)wgs * 256 * sizeof(u64);
+	if (c.rdtab.ensure(bytes) != RSX_OK) {
+		(void)hipGetLastError();
+		return RSX_OK;   // (not an error: the caller takes the sort)
+	}
+	u64 *tab = (u64 *)c.rdtab.p;
+	const u64 *offs = (const u64 *)(c.ghist() + 256 * col);
+	hipLaunchKernelGGL((rsx_rankdata_digits_kernel<KT>), dim3(wgs), dim3(RANKDATA_PLACE_THREADS), 0, c.stream, src, (u64)n, share, 8 * col, ka, tab);
+	hipLaunchKernelGGL(rsx_rankdata_bases_kernel, dim3(1), dim3(1024), 0, c.stream, tab, wgs, offs);
+	hipLaunchKernelGGL((rsx_rankdata_place_kernel<KT, IT>), dim3(wgs), dim3(RANKDATA_PLACE_THREADS), 0, c.stream, src, (u64)n, share, 8 * col, ka,
+	                   (const u64 *)tab, place);
+	HIP_TRY(hipGetLastError());
+	info->table_bytes += bytes;
+	*done = 1;
+	return RSX_OK;
+}
+
+// less and equal of every key from the exclusive offsets of its packed value (in_lds: one column's 256, else 65537)
+template <typename KT, typename IT>
+int rankdata_lookup(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, const BitRuns &runs, const u64 *offs, bool in_lds, IT *less, IT *equal)
+{
+	// (as group_lookup: two workgroups of 1024 threads fill a CU, each with a few sweeps of its own)
+	const u64 nvec = (u64)n * sizeof(KT) / 16;
+	const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>(512, nvec / 16384));
+	if (in_lds)
+		hipLaunchKernelGGL((rsx_rankdata_lookup_kernel<KT, IT, true>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, offs, less, equal);
+	else
+		hipLaunchKernelGGL((rsx_rankdata_lookup_kernel<KT, IT, false>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, offs, less, equal);
+	HIP_TRY(hipGetLastError());
+	return RSX_OK;
+}
+
+// route 2: the counts of the packed varying bits (at most 16 of them), their scan, the lookup.  *done = 0: no room.
+template <typename KT, typename IT>
+int rankdata_count16(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, const BitRuns &runs, IT *less, IT *equal, rsx_rankdata_info *info, int *done)
+{
+	*done = 0;
+	if constexpr (sizeof(KT) >= 2) {
+		if (c.rdtab.ensure(RANKDATA_TAB16_BYTES) != RSX_OK) {
+			(void)hipGetLastError();
+			return RSX_OK;
+		}
+		u32 *jt = (u32 *)c.rdtab.p;
+		u64 *offs = (u64 *)((char *)c.rdtab.p + 65536 * sizeof(u32));
+		HIP_TRY(hipMemsetAsync(jt, 0, 65536 * sizeof(u32), c.stream));
+		hipLaunchKernelGGL((rsx_rankdata_count16_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, jt);
+		hipLaunchKernelGGL(rsx_rankdata_scan16_kernel, dim3(1), dim3(1024), 0, c.stream, (const u32 *)jt, offs, (u64)n);
+		HIP_TRY(hipGetLastError());
+		RSX_TRY((rankdata_lookup<KT, IT>(c, src, n, ka, runs, offs, false, less, equal)));
+		info->route = RSX_RANKDATA_COUNT16;
+		info->table_bytes = RANKDATA_TAB16_BYTES;
+		*done = 1;
+	}
+	return RSX_OK;
+}
+
+// route 3: the stable key + index sort of a workspace copy as group_by_sort sets it up (none where the plan found the input
+// sorted), then the permutation inverted, or -- for less and equal -- the heads, their positions and the runs pass
+template <typename KT, typename IT>
+int rankdata_by_sort(Ctx &c, const KT *src, size_t n, int dtype, int order, bool sorted, const RankdataOut<IT> &out, rsx_rankdata_info *info)
+{
+	info->route = RSX_RANKDATA_SORT;
+	const size_t npad = (n + 63) & ~(size_t)63;
+	const KT *in = src;
+	const IT *perm = nullptr;
+	IT *spare = nullptr;   // n indices nobody holds: the half of vals[0] the result is not in
+	if (!sorted) {
+		RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
+		RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
+		RSX_TRY(c.vals[0].ensure(2 * npad * sizeof(IT)));
+		KT *k0 = (KT *)c.keys[0].p, *k1 = (KT *)c.keys[1].p;
+		IT *v0 = (IT *)c.vals[0].p, *v1 = v0 + npad;
+		HIP_TRY(hipMemcpyAsync(k0, src, n * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
+		hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, v0, (u64)n);
+		HIP_TRY(hipGetLastError());
+		rsx_info si;
+		info_clear(&si, dtype);
+		RSX_TRY((sort_pairs_device<KT, IT>(c, k0, k1, v0, v1, n, dtype, order, &si)));
+		info->sort = si;
+		in = si.result_in_aux ? k1 : k0;
+		perm = si.result_in_aux ? v1 : v0;
+		spare = si.result_in_aux ? v0 : v1;
+	}
+	if (!out.less && !out.equal) {
+		if (perm)
+			hipLaunchKernelGGL((rsx_rankdata_inverse_kernel<IT>), dim3(2048), dim3(256), 0, c.stream, perm, (u64)n, out.place);
+		else
+			hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, out.place, (u64)n);
+		HIP_TRY(hipGetLastError());
+		return RSX_OK;
+	}
+	if (!spare) {
+		RSX_TRY(c.vals[0].ensure(npad * sizeof(IT)));
+		spare = (IT *)c.vals[0].p;
+	}
+	const u64 tiles = ((u64)n + unique_heads_tile<KT>() - 1) / unique_heads_tile<KT>();
+	RSX_TRY(c.urecs.ensure(64 + (size_t)tiles * sizeof(UniqueRec)));
+	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 0>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c),
+	                   (KT *)nullptr, (void *)nullptr, 0u);
+	hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), tiles, unique_hdr(c));
+	// (the positions of the heads: what rsx_group_heads_kernel calls `first` over the identity permutation)
+	hipLaunchKernelGGL((rsx_group_heads_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (const IT *)nullptr, (u64)n,
+	                   (const UniqueRec *)unique_recs(c), (IT *)nullptr, (KT *)nullptr, (IT *)nullptr, spare);
+	hipLaunchKernelGGL((rsx_rankdata_runs_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, perm, (u64)n,
+	                   (const UniqueRec *)unique_recs(c), (const IT *)spare, (const u64 *)unique_hdr(c), out.place, out.less, out.equal);
+	HIP_TRY(hipGetLastError());
+	return RSX_OK;
+}
+
+template <typename KT, typename IT>
+int sort_rankdata_device(Ctx &c, const KT *src, size_t n, int dtype, int order, const RankdataOut<IT> &out, rsx_rankdata_info *info)
+{
+	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
+	const bool tables = !env().rankdata_no_tables;
+	RSX_TRY(c.urecs.ensure(64 + 64 * sizeof(UniqueRec)));
+	bool to_sort = false, sorted = false;
+	if (unique_sample_wanted<KT>(c, n)) {
+		// (as sort_group_device: the sample can only PROVE that many bits vary -- more than any table here takes)
+		const u64 init[2] = {0, ~0ull};
+		u64 got[2];
+		HIP_TRY(hipMemcpyAsync(unique_hdr(c), init, sizeof init, hipMemcpyHostToDevice, c.stream));
+		hipLaunchKernelGGL((rsx_unique_sample_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, src, (u64)n, ka, unique_hdr(c));
+		HIP_TRY(hipGetLastError());
+		HIP_TRY(hipMemcpyAsync(got, unique_hdr(c), sizeof got, hipMemcpyDeviceToHost, c.stream));
+		HIP_TRY(hipStreamSynchronize(c.stream));
+		const u32 limit = !tables ? 0u : out.place ? 8u : 16u;   // (the place: one kept column at most)
+		to_sort = (u32)__builtin_popcountll(got[0] ^ got[1]) > limit;
+	}
+	if (!to_sort) {
+		Plan plan{};
+		RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, 0));
+		info_from_plan(&info->sort, plan);
+		const u64 vary = ((u64)plan.vary_hi << 32) | plan.vary_lo;
+		const u32 vbits = (u32)__builtin_popcountll(vary);
+		info->varying_bits = vbits;
+		sorted = plan.sorted != 0;
+		if (sorted)
+			info->sort.early_exit = 2;
+		if (vary == 0) {
+			// every key equal: the input order is the sorted order, nothing is smaller, all n are equal
+			info->route = RSX_RANKDATA_TRIVIAL;
+			if (out.place)
+				hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, out.place, (u64)n);
+			if (out.less)
+				HIP_TRY(hipMemsetAsync(out.less, 0, n * sizeof(IT), c.stream));
+			if (out.equal)
+				hipLaunchKernelGGL((rsx_rankdata_fill_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, out.equal, (u64)n, (IT)n);
+			HIP_TRY(hipGetLastError());
+			return RSX_OK;
+		}
+		if (tables && plan.ncols == 1) {
+			// one kept column: its 256 exclusive offsets lie in the plan's histogram -- less and equal are lookups, the place is
+			// the address a counting sort's scatter would compute
+			const u32 col = plan.cols[0];
+			info->table_bytes = 256 * sizeof(u64);
+			int done = 1;
+			if (out.place)
+				RSX_TRY((rankdata_place<KT, IT>(c, src, n, ka, col, out.place, info, &done)));
+			if (done) {
+				if (out.less || out.equal) {
+					BitRuns runs{};
+					runs.n = 1;
+					runs.src[0] = (uint8_t)(8 * col);
+					runs.len[0] = 8;
+					runs.dst[0] = 0;
+					RSX_TRY((rankdata_lookup<KT, IT>(c, src, n, ka, runs, (const u64 *)(c.ghist() + 256 * col), true, out.less, out.equal)));
+				}
+				info->route = RSX_RANKDATA_TABLE;
+				return RSX_OK;
+			}
+			info->table_bytes = 0;
+		}
+		BitRuns runs;
+		// (2^16 counters are what the LDS scheme holds, and a counter of 32 bits may have to hold n)
+		if (tables && !out.place && sizeof(KT) >= 2 && vbits <= 16 && (u64)n < (1ull << 32) && bit_runs(vary, &runs)) {
+			int done = 0;
+			RSX_TRY((rankdata_count16<KT, IT>(c, src, n, ka, runs, out.less, out.equal, info, &done)));
+			if (done)
+				return RSX_OK;
+		}
+	}
+	return rankdata_by_sort<KT, IT>(c, src, n, dtype, order, sorted, out, info);
+}
+
+}  // namespace
+
+extern "C" {
+
+/* ---- rsx_sort_rankdata: every element's place in the sorted order (rsx_rankdata.hpp) ---- */
+static int rankdata_args(const char *who, const void *src, size_t n, rsx_dtype dtype, rsx_order order, const void *place, const void *less,
+                         const void *equal, size_t idx_bytes)
+{
+	if (!dtype_size(dtype) || (order != RSX_ASCENDING && order != RSX_DESCENDING) || (n && !src))
+		return fail(RSX_EINVAL, "%s: bad argument", who);
+	if (!place && !less && !equal)
+		return fail(RSX_EINVAL, "%s: all three outputs are NULL", who);
+	if (idx_bytes != 4 && idx_bytes != 8)
+		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
+	if (idx_bytes == 4 && (uint64_t)n > 0xFFFFFFFFull)   // (equal may be n itself)
+		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
+	return RSX_OK;
+}
+
+int rsx_sort_rankdata_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_order order, void *d_out_place, void *d_out_less,
+                             void *d_out_equal, size_t idx_bytes, void *stream, rsx_rankdata_info *info)
+{
+	rsx_rankdata_info local;
+	info = info_or(info, &local);
+	info_clear(&info->sort, dtype);
+	RSX_TRY(rankdata_args("rsx_sort_rankdata_device", d_src, n, dtype, order, d_out_place, d_out_less, d_out_equal, idx_bytes));
+	if (n == 0) {
+		info->sort.early_exit = 1;
+		return RSX_OK;
+	}
+	RSX_LOCKED_CTX(c, stream);
+	RSX_TRY(refuse_capture(stream, "rsx_sort_rankdata_device", "the call waits for the plan of the keys"));
+	if (n == 1) {
+		// (one key: at place 0, nothing below it, itself equal)
+		const u64 one64 = 1;
+		const u32 one32 = 1;
+		if (d_out_place)
+			HIP_TRY(hipMemsetAsync(d_out_place, 0, idx_bytes, c->stream));
+		if (d_out_less)
+			HIP_TRY(hipMemsetAsync(d_out_less, 0, idx_bytes, c->stream));
+		if (d_out_equal) {
+			HIP_TRY(hipMemcpyAsync(d_out_equal, idx_bytes == 4 ? (const void *)&one32 : (const void *)&one64, idx_bytes, hipMemcpyHostToDevice,
+			                       c->stream));
+			HIP_TRY(hipStreamSynchronize(c->stream));
+		}
+		info->sort.early_exit = 1;
+		return RSX_OK;
+	}
+	RSX_DISPATCH_KT_W(dtype, idx_bytes, IT,
+	                  return (sort_rankdata_device<KT, IT>(*c, (const KT *)d_src, n, dtype, order,
+	                                                       RankdataOut<IT>{(IT *)d_out_place, (IT *)d_out_less, (IT *)d_out_equal}, info)));
+	return RSX_OK;
+}
+
+int rsx_sort_rankdata(const void *src, size_t n, rsx_dtype dtype, rsx_order order, void *out_place, void *out_less, void *out_equal,
+                      size_t idx_bytes, rsx_rankdata_info *info)
+{
+	rsx_rankdata_info local;
+	info = info_or(info, &local);
+	info_clear(&info->sort, dtype);
+	const size_t kb = dtype_size(dtype);
+	RSX_TRY(rankdata_args("rsx_sort_rankdata", src, n, dtype, order, out_place, out_less, out_equal, idx_bytes));
+	if (n == 0) {
+		info->sort.early_exit = 1;
+		return RSX_OK;
+	}
+	if (one_on_host(n, src)) {
+		if (out_place)
+			memset(out_place, 0, idx_bytes);
+		if (out_less)
+			memset(out_less, 0, idx_bytes);
+		if (out_equal) {
+			if (idx_bytes == 4)
+				*(uint32_t *)out_equal = 1;
+			else
+				*(uint64_t *)out_equal = 1;
+		}
+		info->sort.early_exit = 1;
+		return RSX_OK;
+	}
+	RSX_LOCKED_CTX(c, nullptr);
+	void *const outs[3] = {out_place, out_less, out_equal};
+	if (is_device_ptr(src)) {
+		for (void *o : outs)
+			if (o && !is_device_ptr(o))
+				return fail(RSX_EINVAL, "rsx_sort_rankdata: src is a device pointer but an output is not");
+		RSX_TRY(rsx_sort_rankdata_device(src, n, dtype, order, out_place, out_less, out_equal, idx_bytes, nullptr, info));
+		HIP_TRY(hipStreamSynchronize(c->stream));
+		return RSX_OK;
+	}
+	// host buffers: the keys staged in recs[0] as rsx_sort_rank stages them, the outputs in [place][less][equal]
+	const size_t ipad = (n * idx_bytes + 255) & ~(size_t)255;
+	RSX_TRY(c->recs[0].ensure(n * kb));
+	RSX_TRY(c->rdout.ensure(3 * ipad));
+	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
+	char *dout[3];
+	for (int i = 0; i < 3; ++i)
+		dout[i] = outs[i] ? (char *)c->rdout.p + (size_t)i * ipad : nullptr;
+	RSX_TRY(rsx_sort_rankdata_device(c->recs[0].p, n, dtype, order, dout[0], dout[1], dout[2], idx_bytes, nullptr, info));
+	for (int i = 0; i < 3; ++i)
+		if (outs[i])
+			HIP_TRY(hipMemcpyAsync(outs[i], dout[i], n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
+	HIP_TRY(hipStreamSynchronize(c->stream));
+	return RSX_OK;
+}
+
+}  // extern "C"
