@@ -309,8 +309,9 @@ int rsx_verify_poll(void *stream, uint64_t *mismatches);
  * rsx_info.hybrid: 5 = no histogram, two MSB passes into slots and leaves; 1 = one MSB pass and leaves; 0 = histogram and one
  * pass per kept column (also: sorted input, and the one-launch sort of small arrays).  The loop all of them stand for is
  * radix_sort.hpp:82-90.  Replaying a captured graph of such a sort re-decides the route on the device each time; what this
- * reports is the last replay's.  The words it reads are the context's: a BLOCKING sort on the same stream between the
- * device-scheduled sort and this call overwrites them (ask before that sort, or use another stream for it). */
+ * reports is the last replay's.  The plan it reads is the device-scheduled sorts' own; the control block of an attempt
+ * without a histogram is the context's: a BLOCKING sort of 2^22 keys or more on the same stream between the device-scheduled
+ * sort and this call may overwrite it (ask before that sort, or use another stream for it). */
 int rsx_async_route(void *stream, uint32_t *route);
 
 /* rs_sort_main / rs_sort_rank with a caller-supplied Hist (radix_sort.hpp:28-33,

@@ -115,8 +115,9 @@ int plan_phase(Ctx &c, const KT *d_src, size_t n, KdfArgs<KT> ka, Plan *out, siz
 	if (c.hist.external)
 		RSX_TRY(c.hist.ensure(hist_bytes));
 	// (fuse_ok: the blocking entry points only.  A captured graph replays the SAME launch, so it cannot alternate between
-	// the two sets of flags: the device-scheduled *_async sorts keep the separate zeroing launch.)
-	if (fuse_ok && status_total && !out && !c.small.external && !env().no_fused_hist) {
+	// the two sets of flags: the device-scheduled *_async sorts keep the separate zeroing launch, and a set of their own
+	// (Ctx::ASYNC_SET) -- a replay between two blocking sorts would otherwise fill the set the second one trusts to be zero.)
+	if (fuse_ok && status_total && !out && !c.small.external && c.gen < Ctx::ASYNC_SET && !env().no_fused_hist) {
 		// Small arrays: the histogram kernel also zeroes (no launch for that).  The set of flags / histogram this sort uses
 		// was zeroed by the previous sort (or at start-up); this sort's histogram kernel zeroes the other set for the next
 		// one, and the status words of its own passes (which run after it).  One workgroup then makes the plan.
@@ -1506,6 +1507,7 @@ int rsx_sort_inplace_async(void *d_buf, void *d_scratch, size_t n, rsx_dtype dty
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
+	AsyncSetScope set_scope(*c);
 	RSX_DISPATCH_KT(dtype, return sort_keys_inplace_async<KT>(*c, (KT *)d_buf, (KT *)d_scratch, n, dtype, order));
 	return RSX_OK;
 }
@@ -1518,6 +1520,7 @@ int rsx_sort_inplace_async_hint(void *d_buf, void *d_scratch, size_t n, rsx_dtyp
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
+	AsyncSetScope set_scope(*c);
 	struct HintScope {   // (the sample kernel of the attempt enqueued by this call reads them: blind_enqueue)
 		Ctx &c;
 		HintScope(Ctx &c_, u32 h) : c(c_) { c.hints = h; }
@@ -1643,6 +1646,7 @@ int rsx_sort_pairs_inplace_async(void *d_keys, void *d_keys_scratch, void *d_val
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
+	AsyncSetScope set_scope(*c);
 	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_inplace_async<KT, VT>(*c, (KT *)d_keys, (KT *)d_keys_scratch, (VT *)d_vals,
 	                                                                                     (VT *)d_vals_scratch, n, dtype, order)));
 	return RSX_OK;
@@ -1694,6 +1698,7 @@ int rsx_sort_rank_inplace_async(const void *d_src, void *d_index_buffer, size_t 
 		return RSX_OK;                       // radix_sort_rank.hpp:28-32
 	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
+	AsyncSetScope set_scope(*c);
 	if (n == 1) {
 		HIP_TRY(hipMemsetAsync(d_index_buffer, 0, idx_bytes, c->stream));
 		return RSX_OK;
@@ -1732,7 +1737,7 @@ int rsx_async_route(void *stream, uint32_t *route)
 	if (c->async_small)
 		return RSX_OK;   // (the one-launch sort writes no device-side plan: what lies there is an earlier sort's)
 	Plan plan;
-	HIP_TRY(hipMemcpy(&plan, c->plan(), sizeof(plan), hipMemcpyDeviceToHost));
+	HIP_TRY(hipMemcpy(&plan, c->async_plan(), sizeof(plan), hipMemcpyDeviceToHost));
 	if (c->async_tried_blind && c->seg.p) {
 		SegCtl ctl;
 		HIP_TRY(hipMemcpy(&ctl, c->seg.p, sizeof(ctl), hipMemcpyDeviceToHost));
@@ -2001,6 +2006,7 @@ int rsx_msd_split_async(const void *d_src, void *d_dst, size_t n, rsx_dtype dtyp
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, stream);
 	AsyncScope async_scope((hipStream_t)stream);
+	AsyncSetScope set_scope(*c);
 	HIP_TRY(hipMemsetAsync(c->small_set(), 0, 256, c->stream));
 	RSX_DISPATCH_KT(dtype, return msd_split_known<KT>(*c, (const KT *)d_src, (KT *)d_dst, n, dtype, order, col, (const u64 *)d_hist, hot));
 	return RSX_OK;

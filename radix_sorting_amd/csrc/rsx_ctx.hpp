@@ -243,7 +243,11 @@ struct Ctx {
 	// The library's own contexts hold TWO sets of flags and histograms and alternate between them (`gen`): small sorts zero
 	// the set of the next sort inside this sort's histogram kernel instead of launching a kernel for it (plan_phase).  A
 	// context in a caller's workspace (external) has one set.
+	// A THIRD set (ASYNC_SET) belongs to the device-scheduled sorts (*_inplace_async, rsx_msd_split_async: AsyncSetScope): a
+	// graph captured from one keeps the addresses it was enqueued with and may be replayed between any two blocking sorts
+	// without the host seeing it, so it must never count into a set that a blocking sort trusts to be zero.
 	u32 gen = 0;
+	static constexpr u32 ASYNC_SET = 2, SETS = 3;
 	static constexpr size_t SMALL_BYTES = 256, HIST_SET_BYTES = 8 * 256 * sizeof(u64);
 	char *small_set() const { return (char *)small.p + (small.external ? 0 : gen * SMALL_BYTES); }
 	char *small_set_other() const { return (char *)small.p + (gen ^ 1u) * SMALL_BYTES; }
@@ -254,16 +258,18 @@ struct Ctx {
 	u64 *verify_bad() const { return (u64 *)(small_set() + 56); }  // RSX_VERIFY: mismatches found by rsx_verify_tile_kernel
 	u32 *hotd() const { return (u32 *)(small_set() + 16); }   // [8] hot digits per column + [1] valid bits (rsx_plan_kernel)
 	Plan *plan() const { return (Plan *)(small_set() + 64); }
+	// ... of the last device-scheduled sort of this context (rsx_async_route), whatever the blocking sorts have done since
+	const Plan *async_plan() const { return (const Plan *)((char *)small.p + (small.external ? 0 : ASYNC_SET * SMALL_BYTES) + 64); }
 	u32 *kept() const { return (u32 *)(small_set() + 128); }
 	u32 *colmax() const { return (u32 *)(small_set() + 192); }   // [8] largest bin per column (rsx_plan_kernel, kept[16..])
 
 	int init()
 	{
-		RSX_TRY(small.ensure(2 * SMALL_BYTES));
-		RSX_TRY(hist.ensure(2 * HIST_SET_BYTES));
+		RSX_TRY(small.ensure(SETS * SMALL_BYTES));
+		RSX_TRY(hist.ensure(SETS * HIST_SET_BYTES));
 		RSX_TRY(gscan.ensure(256 * sizeof(u64)));
-		HIP_TRY(hipMemset(small.p, 0, 2 * SMALL_BYTES));   // (both sets start out zeroed: see `gen`)
-		HIP_TRY(hipMemset(hist.p, 0, 2 * HIST_SET_BYTES));
+		HIP_TRY(hipMemset(small.p, 0, SETS * SMALL_BYTES));   // (the alternating sets start out zeroed: see `gen`)
+		HIP_TRY(hipMemset(hist.p, 0, SETS * HIST_SET_BYTES));
 		if (!host_plan)
 		{
 			HIP_TRY(hipHostMalloc((void **)&host_plan, sizeof(Plan), hipHostMallocMapped));
@@ -351,6 +357,17 @@ struct Ctx {
 		host_plan = nullptr;
 		host_hist = nullptr;
 	}
+};
+
+// ... for the duration of a device-scheduled entry point on one of the library's own contexts (held under the context's mutex):
+// every accessor above then names the third set, and `gen` is what it was when the call returns
+struct AsyncSetScope {
+	Ctx &c;
+	u32 prev;
+	explicit AsyncSetScope(Ctx &c_) : c(c_), prev(c_.gen) { c.gen = Ctx::ASYNC_SET; }
+	~AsyncSetScope() { c.gen = prev; }
+	AsyncSetScope(const AsyncSetScope &) = delete;
+	AsyncSetScope &operator=(const AsyncSetScope &) = delete;
 };
 
 std::mutex g_mu;
