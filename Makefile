@@ -16,44 +16,21 @@ radix_sorting_amd/librsx.so: $(CSRC)/rsx.hip $(wildcard $(CSRC)/*.hpp) include/r
 oracle: lib
 	$(MAKE) -C oracle
 
-# C++ check of the template surface in include/ (needs a GPU to run: tests/test_gpu_cpp.py)
-cpp: tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/rankdata_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check
+# C++ checks of the template surface in include/ (they need a GPU to run: tests/test_gpu_cpp.py) ...
+LIB_CHECKS  = dropin_check unique_check group_check rankdata_check topk_check lex_check nth_check
+# ... and of one pure header of the host side each, tests/cpp/X_check of $(CSRC)/rsx_X.hpp, on the CPU (no GPU, no library:
+# tests/test_env_cpu.py, tests/test_seg_layout_cpu.py, tests/test_keybits_cpu.py)
+PURE_CHECKS = env_check seg_layout_check keybits_check
+CHECKS      = $(addprefix tests/cpp/,$(LIB_CHECKS) $(PURE_CHECKS))
 
-tests/cpp/dropin_check: tests/cpp/dropin_check.cpp include/radix_sort.hpp include/radix_sort_rank.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/dropin_check.cpp -Lradix_sorting_amd -lrsx \
+cpp: $(CHECKS)
+
+$(addprefix tests/cpp/,$(LIB_CHECKS)): tests/cpp/%: tests/cpp/%.cpp include/radix_sort.hpp include/radix_sort_rank.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
+	g++ -std=gnu++17 -O2 -Wall -Iinclude $< -Lradix_sorting_amd -lrsx \
 	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
 
-tests/cpp/unique_check: tests/cpp/unique_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/unique_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-tests/cpp/group_check: tests/cpp/group_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/group_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-tests/cpp/rankdata_check: tests/cpp/rankdata_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/rankdata_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-tests/cpp/topk_check: tests/cpp/topk_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/topk_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-tests/cpp/lex_check: tests/cpp/lex_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/lex_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-tests/cpp/nth_check: tests/cpp/nth_check.cpp include/radix_sort.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude tests/cpp/nth_check.cpp -Lradix_sorting_amd -lrsx \
-	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
-
-# the RSX_* switches on the CPU (no GPU, no library: tests/test_env_cpu.py)
-tests/cpp/env_check: tests/cpp/env_check.cpp $(CSRC)/rsx_env.hpp
-	g++ -std=gnu++17 -O2 -Wall tests/cpp/env_check.cpp -o $@
-
-# the segmented routes' control-block layout and slot placement on the CPU (no GPU, no library: tests/test_seg_layout_cpu.py)
-tests/cpp/seg_layout_check: tests/cpp/seg_layout_check.cpp $(CSRC)/rsx_seg_layout.hpp
-	g++ -std=gnu++17 -O2 -Wall tests/cpp/seg_layout_check.cpp -o $@
+$(addprefix tests/cpp/,$(PURE_CHECKS)): tests/cpp/%_check: tests/cpp/%_check.cpp $(CSRC)/rsx_%.hpp
+	g++ -std=gnu++17 -O2 -Wall $< -o $@
 
 # counterparts of the reference's `radix` and `radix_bench` commands on this repo's headers (tools/radix.cpp, tools/radix_bench.cpp)
 cli: tools/radix tools/radix_bench
@@ -67,7 +44,7 @@ tools/radix_bench: tools/radix_bench.cpp include/radix_sort.hpp include/radix_so
 	-L/opt/rocm/lib -lamdhip64 -Wl,-rpath,'$$ORIGIN/../radix_sorting_amd' -Wl,-rpath,/opt/rocm/lib -o $@
 
 clean:
-	rm -f radix_sorting_amd/librsx.so tests/cpp/dropin_check tests/cpp/unique_check tests/cpp/group_check tests/cpp/rankdata_check tests/cpp/topk_check tests/cpp/lex_check tests/cpp/nth_check tests/cpp/env_check tests/cpp/seg_layout_check tools/radix tools/radix_bench
+	rm -f radix_sorting_amd/librsx.so $(CHECKS) tools/radix tools/radix_bench
 	$(MAKE) -C oracle clean
 
 .PHONY: all lib oracle cpp cli clean

@@ -1031,31 +1031,6 @@ int rank_pass(Ctx &c, const void *kin, void *kout, u32 out_bytes, const IT *vin,
 	return scatter_pass_to<KCUR, IT>(c, (const KCUR *)kin, kout, out_bytes, vin, vout, n, shift, gbase, ka, flags, oshift);
 }
 
-// the runs of contiguous set bits of `mask`, lowest first, packed towards bit 0; false if there are more than eight
-bool bit_runs(u64 mask, BitRuns *out)
-{
-	out->n = 0;
-	u32 dst = 0;
-	for (u32 b = 0; b < 64;) {
-		if (!((mask >> b) & 1)) {
-			++b;
-			continue;
-		}
-		u32 e = b;
-		while (e < 64 && ((mask >> e) & 1))
-			++e;
-		if (out->n == 8)
-			return false;
-		out->src[out->n] = (uint8_t)b;
-		out->len[out->n] = (uint8_t)(e - b);
-		out->dst[out->n] = (uint8_t)dst;
-		dst += e - b;
-		++out->n;
-		b = e;
-	}
-	return true;
-}
-
 // want_half: -1 = the half the number of kept columns dictates (radix_sort_rank.hpp:91); 0 / 1 = leave the ranks in that half
 // whatever the number of passes is (the first pass generates its indices, so it can write to either half).
 template <typename KT, typename IT>
@@ -1937,6 +1912,7 @@ int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype
 }  // extern "C"
 
 // one file per feature: its host driver (anonymous namespace) and its entry points (extern "C")
+#include "rsx_keybits_api.hpp"   // what the next three share: the sample and the plan, the bitmap, the heads, the index sort
 #include "rsx_unique_api.hpp"    // rsx_sort_unique[_device]
 #include "rsx_group_api.hpp"     // rsx_sort_group[_device]
 #include "rsx_rankdata_api.hpp"  // rsx_sort_rankdata[_device]

@@ -51,15 +51,17 @@ template <typename T> T *info_or(T *info, T *local)
 	return info;
 }
 
-// the width of the indices a call writes, and whether n fits it
-int idx_args(const char *who, size_t idx_bytes, size_t n)
+// the width of the indices a call of n keys writes, and whether the largest of them fits it: n - 1 where they are positions
+// (idx_last), n itself where they may be counts
+int idx_args(const char *who, size_t idx_bytes, size_t n, size_t largest)
 {
 	if (idx_bytes != 4 && idx_bytes != 8)
 		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
-	if (idx_bytes == 4 && (uint64_t)n > (1ull << 32))
+	if (idx_bytes == 4 && (uint64_t)largest > 0xFFFFFFFFull)
 		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
 	return RSX_OK;
 }
+inline size_t idx_last(size_t n) { return n ? n - 1 : 0; }
 
 // rsx_sort_topk*, rsx_sort_nth*: keys of one type in, keys and / or their indices out
 int select_args(const char *who, const void *src, size_t n, rsx_dtype dtype, rsx_order order, const void *out_keys, const void *out_idx,
@@ -69,7 +71,7 @@ int select_args(const char *who, const void *src, size_t n, rsx_dtype dtype, rsx
 		return fail(RSX_EINVAL, "%s: bad argument", who);
 	if (!out_keys && !out_idx)
 		return fail(RSX_EINVAL, "%s: both outputs are NULL", who);
-	return idx_args(who, idx_bytes, n);
+	return idx_args(who, idx_bytes, n, idx_last(n));
 }
 
 // ... the host entry point behind its checks.  run(keys, out_keys, out_idx) is the _device entry point: on the caller's buffers where

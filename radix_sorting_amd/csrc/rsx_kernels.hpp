@@ -33,6 +33,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "rsx_keybits.hpp"   // BitRuns and the host arithmetic over the varying bits
+
 namespace rsx {
 
 typedef unsigned long long u64;
@@ -1074,12 +1076,7 @@ __global__ __launch_bounds__(64) void rsx_verify_tile_kernel(const KT *__restric
 // README.md:716-758 "key compaction": dst[i] = the varying bits of kdf(src[i]) packed together (a software bit extract
 // over at most 8 runs of contiguous mask bits).  All other bits are the same in every key, so the packed values order
 // exactly as the keys do; a rank sort of them needs ceil(varying bits / 8) passes instead of one per varying byte.
-struct BitRuns {
-	uint8_t n;            // runs
-	uint8_t src[8];       // first bit of the run in the key
-	uint8_t len[8];       // bits
-	uint8_t dst[8];       // first bit of the run in the packed value
-};
+// (BitRuns: rsx_keybits.hpp)
 template <typename KT, typename OT>
 __global__ __launch_bounds__(256) void rsx_compact_bits_kernel(const KT *__restrict__ src, OT *__restrict__ dst, u64 n, KdfArgs<KT> ka,
                                                                BitRuns runs)

@@ -157,7 +157,7 @@ static int lex_args_check(const char *who, const rsx_lex_col *cols, size_t ncols
 		if (n && !cols[i].data)
 			return fail(RSX_EINVAL, "%s: column %zu is NULL", who, i);
 	}
-	RSX_TRY(idx_args(who, idx_bytes, out_idx ? n : 0));   // (a missing output is reported before an n that does not fit)
+	RSX_TRY(idx_args(who, idx_bytes, n, out_idx ? idx_last(n) : 0));   // (a missing output is reported before an n that does not fit)
 	if (n && !out_idx)
 		return fail(RSX_EINVAL, "%s: the output is NULL", who);
 	return RSX_OK;

@@ -24,10 +24,8 @@ int rankdata_place(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, u32 col, IT 
 	const u64 share = (per + RANKDATA_PLACE_TILE - 1) / RANKDATA_PLACE_TILE * RANKDATA_PLACE_TILE;
 	const u32 wgs = (u32)(((u64)n + share - 1) / share);
 	const size_t bytes = (size_t)wgs * 256 * sizeof(u64);
-	if (c.rdtab.ensure(bytes) != RSX_OK) {
-		(void)hipGetLastError();
+	if (c.rdtab.ensure(bytes) != RSX_OK)
 		return RSX_OK;   // (not an error: the caller takes the sort)
-	}
 	u64 *tab = (u64 *)c.rdtab.p;
 	const u64 *offs = (const u64 *)(c.ghist() + 256 * col);
 	hipLaunchKernelGGL((rsx_rankdata_digits_kernel<KT>), dim3(wgs), dim3(RANKDATA_PLACE_THREADS), 0, c.stream, src, (u64)n, share, 8 * col, ka, tab);
@@ -45,8 +43,7 @@ template <typename KT, typename IT>
 int rankdata_lookup(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, const BitRuns &runs, const u64 *offs, bool in_lds, IT *less, IT *equal)
 {
 	// (as group_lookup: two workgroups of 1024 threads fill a CU, each with a few sweeps of its own)
-	const u64 nvec = (u64)n * sizeof(KT) / 16;
-	const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>(512, nvec / 16384));
+	const unsigned grid = sweep_grid(n, sizeof(KT));
 	if (in_lds)
 		hipLaunchKernelGGL((rsx_rankdata_lookup_kernel<KT, IT, true>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, offs, less, equal);
 	else
@@ -61,10 +58,8 @@ int rankdata_count16(Ctx &c, const KT *src, size_t n, KdfArgs<KT> ka, const BitR
 {
 	*done = 0;
 	if constexpr (sizeof(KT) >= 2) {
-		if (c.rdtab.ensure(RANKDATA_TAB16_BYTES) != RSX_OK) {
-			(void)hipGetLastError();
+		if (c.rdtab.ensure(RANKDATA_TAB16_BYTES) != RSX_OK)
 			return RSX_OK;
-		}
 		u32 *jt = (u32 *)c.rdtab.p;
 		u64 *offs = (u64 *)((char *)c.rdtab.p + 65536 * sizeof(u32));
 		HIP_TRY(hipMemsetAsync(jt, 0, 65536 * sizeof(u32), c.stream));
@@ -85,49 +80,27 @@ template <typename KT, typename IT>
 int rankdata_by_sort(Ctx &c, const KT *src, size_t n, int dtype, int order, bool sorted, const RankdataOut<IT> &out, rsx_rankdata_info *info)
 {
 	info->route = RSX_RANKDATA_SORT;
-	const size_t npad = (n + 63) & ~(size_t)63;
-	const KT *in = src;
-	const IT *perm = nullptr;
-	IT *spare = nullptr;   // n indices nobody holds: the half of vals[0] the result is not in
-	if (!sorted) {
-		RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-		RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
-		RSX_TRY(c.vals[0].ensure(2 * npad * sizeof(IT)));
-		KT *k0 = (KT *)c.keys[0].p, *k1 = (KT *)c.keys[1].p;
-		IT *v0 = (IT *)c.vals[0].p, *v1 = v0 + npad;
-		HIP_TRY(hipMemcpyAsync(k0, src, n * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
-		hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, v0, (u64)n);
-		HIP_TRY(hipGetLastError());
-		rsx_info si;
-		info_clear(&si, dtype);
-		RSX_TRY((sort_pairs_device<KT, IT>(c, k0, k1, v0, v1, n, dtype, order, &si)));
-		info->sort = si;
-		in = si.result_in_aux ? k1 : k0;
-		perm = si.result_in_aux ? v1 : v0;
-		spare = si.result_in_aux ? v0 : v1;
-	}
+	IndexSorted<KT, IT> s;
+	RSX_TRY((keybits_index_sort<KT, IT>(c, src, n, dtype, order, sorted, &info->sort, &s)));
 	if (!out.less && !out.equal) {
-		if (perm)
-			hipLaunchKernelGGL((rsx_rankdata_inverse_kernel<IT>), dim3(2048), dim3(256), 0, c.stream, perm, (u64)n, out.place);
+		if (s.perm)
+			hipLaunchKernelGGL((rsx_rankdata_inverse_kernel<IT>), dim3(2048), dim3(256), 0, c.stream, s.perm, (u64)n, out.place);
 		else
 			hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, out.place, (u64)n);
 		HIP_TRY(hipGetLastError());
 		return RSX_OK;
 	}
-	if (!spare) {
-		RSX_TRY(c.vals[0].ensure(npad * sizeof(IT)));
-		spare = (IT *)c.vals[0].p;
+	if (!s.spare) {
+		RSX_TRY(c.vals[0].ensure(((n + 63) & ~(size_t)63) * sizeof(IT)));
+		s.spare = (IT *)c.vals[0].p;
 	}
-	const u64 tiles = ((u64)n + unique_heads_tile<KT>() - 1) / unique_heads_tile<KT>();
-	RSX_TRY(c.urecs.ensure(64 + (size_t)tiles * sizeof(UniqueRec)));
-	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 0>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c),
-	                   (KT *)nullptr, (void *)nullptr, 0u);
-	hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), tiles, unique_hdr(c));
+	u64 tiles;
+	RSX_TRY(keybits_heads<KT>(c, s.in, n, &tiles));
 	// (the positions of the heads: what rsx_group_heads_kernel calls `first` over the identity permutation)
-	hipLaunchKernelGGL((rsx_group_heads_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (const IT *)nullptr, (u64)n,
-	                   (const UniqueRec *)unique_recs(c), (IT *)nullptr, (KT *)nullptr, (IT *)nullptr, spare);
-	hipLaunchKernelGGL((rsx_rankdata_runs_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, perm, (u64)n,
-	                   (const UniqueRec *)unique_recs(c), (const IT *)spare, (const u64 *)unique_hdr(c), out.place, out.less, out.equal);
+	hipLaunchKernelGGL((rsx_group_heads_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, s.in, (const IT *)nullptr, (u64)n,
+	                   (const UniqueRec *)unique_recs(c), (IT *)nullptr, (KT *)nullptr, (IT *)nullptr, s.spare);
+	hipLaunchKernelGGL((rsx_rankdata_runs_kernel<KT, IT>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, s.in, s.perm, (u64)n,
+	                   (const UniqueRec *)unique_recs(c), (const IT *)s.spare, (const u64 *)unique_hdr(c), out.place, out.less, out.equal);
 	HIP_TRY(hipGetLastError());
 	return RSX_OK;
 }
@@ -137,31 +110,12 @@ int sort_rankdata_device(Ctx &c, const KT *src, size_t n, int dtype, int order, 
 {
 	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
 	const bool tables = !env().rankdata_no_tables;
-	RSX_TRY(c.urecs.ensure(64 + 64 * sizeof(UniqueRec)));
-	bool to_sort = false, sorted = false;
-	if (unique_sample_wanted<KT>(c, n)) {
-		// (as sort_group_device: the sample can only PROVE that many bits vary -- more than any table here takes)
-		const u64 init[2] = {0, ~0ull};
-		u64 got[2];
-		HIP_TRY(hipMemcpyAsync(unique_hdr(c), init, sizeof init, hipMemcpyHostToDevice, c.stream));
-		hipLaunchKernelGGL((rsx_unique_sample_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, src, (u64)n, ka, unique_hdr(c));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(got, unique_hdr(c), sizeof got, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const u32 limit = !tables ? 0u : out.place ? 8u : 16u;   // (the place: one kept column at most)
-		to_sort = (u32)__builtin_popcountll(got[0] ^ got[1]) > limit;
-	}
-	if (!to_sort) {
-		Plan plan{};
-		RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, 0));
-		info_from_plan(&info->sort, plan);
-		const u64 vary = ((u64)plan.vary_hi << 32) | plan.vary_lo;
-		const u32 vbits = (u32)__builtin_popcountll(vary);
-		info->varying_bits = vbits;
-		sorted = plan.sorted != 0;
-		if (sorted)
-			info->sort.early_exit = 2;
-		if (vary == 0) {
+	KeyBits kb;
+	// (the place: one kept column at most)
+	RSX_TRY(keybits_front<KT>(c, src, n, ka, !tables ? 0u : out.place ? 8u : 16u, &info->sort, &info->varying_bits, &kb));
+	if (kb.planned) {
+		const Plan &plan = kb.plan;
+		if (kb.vary == 0) {
 			// every key equal: the input order is the sorted order, nothing is smaller, all n are equal
 			info->route = RSX_RANKDATA_TRIVIAL;
 			if (out.place)
@@ -182,14 +136,9 @@ int sort_rankdata_device(Ctx &c, const KT *src, size_t n, int dtype, int order, 
 			if (out.place)
 				RSX_TRY((rankdata_place<KT, IT>(c, src, n, ka, col, out.place, info, &done)));
 			if (done) {
-				if (out.less || out.equal) {
-					BitRuns runs{};
-					runs.n = 1;
-					runs.src[0] = (uint8_t)(8 * col);
-					runs.len[0] = 8;
-					runs.dst[0] = 0;
-					RSX_TRY((rankdata_lookup<KT, IT>(c, src, n, ka, runs, (const u64 *)(c.ghist() + 256 * col), true, out.less, out.equal)));
-				}
+				if (out.less || out.equal)
+					RSX_TRY((rankdata_lookup<KT, IT>(c, src, n, ka, column_runs(col), (const u64 *)(c.ghist() + 256 * col), true, out.less,
+					                                 out.equal)));
 				info->route = RSX_RANKDATA_TABLE;
 				return RSX_OK;
 			}
@@ -197,14 +146,14 @@ int sort_rankdata_device(Ctx &c, const KT *src, size_t n, int dtype, int order, 
 		}
 		BitRuns runs;
 		// (2^16 counters are what the LDS scheme holds, and a counter of 32 bits may have to hold n)
-		if (tables && !out.place && sizeof(KT) >= 2 && vbits <= 16 && (u64)n < (1ull << 32) && bit_runs(vary, &runs)) {
+		if (tables && !out.place && sizeof(KT) >= 2 && kb.vbits <= 16 && (u64)n < (1ull << 32) && bit_runs(kb.vary, &runs)) {
 			int done = 0;
 			RSX_TRY((rankdata_count16<KT, IT>(c, src, n, ka, runs, out.less, out.equal, info, &done)));
 			if (done)
 				return RSX_OK;
 		}
 	}
-	return rankdata_by_sort<KT, IT>(c, src, n, dtype, order, sorted, out, info);
+	return rankdata_by_sort<KT, IT>(c, src, n, dtype, order, kb.sorted, out, info);
 }
 
 }  // namespace
@@ -219,11 +168,7 @@ static int rankdata_args(const char *who, const void *src, size_t n, rsx_dtype d
 		return fail(RSX_EINVAL, "%s: bad argument", who);
 	if (!place && !less && !equal)
 		return fail(RSX_EINVAL, "%s: all three outputs are NULL", who);
-	if (idx_bytes != 4 && idx_bytes != 8)
-		return fail(RSX_EINVAL, "%s: idx_bytes = %zu (4 or 8)", who, idx_bytes);
-	if (idx_bytes == 4 && (uint64_t)n > 0xFFFFFFFFull)   // (equal may be n itself)
-		return fail(RSX_EINVAL, "%s: n = %zu does not fit a 4-byte index", who, n);
-	return RSX_OK;
+	return idx_args(who, idx_bytes, n, n);   // (equal may be n itself)
 }
 
 int rsx_sort_rankdata_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_order order, void *d_out_place, void *d_out_less,
@@ -241,17 +186,12 @@ int rsx_sort_rankdata_device(const void *d_src, size_t n, rsx_dtype dtype, rsx_o
 	RSX_TRY(refuse_capture(stream, "rsx_sort_rankdata_device", "the call waits for the plan of the keys"));
 	if (n == 1) {
 		// (one key: at place 0, nothing below it, itself equal)
-		const u64 one64 = 1;
-		const u32 one32 = 1;
 		if (d_out_place)
 			HIP_TRY(hipMemsetAsync(d_out_place, 0, idx_bytes, c->stream));
 		if (d_out_less)
 			HIP_TRY(hipMemsetAsync(d_out_less, 0, idx_bytes, c->stream));
-		if (d_out_equal) {
-			HIP_TRY(hipMemcpyAsync(d_out_equal, idx_bytes == 4 ? (const void *)&one32 : (const void *)&one64, idx_bytes, hipMemcpyHostToDevice,
-			                       c->stream));
-			HIP_TRY(hipStreamSynchronize(c->stream));
-		}
+		if (d_out_equal)
+			RSX_TRY(put_index_device(d_out_equal, idx_bytes, 1, c->stream));
 		info->sort.early_exit = 1;
 		return RSX_OK;
 	}
@@ -278,39 +218,20 @@ int rsx_sort_rankdata(const void *src, size_t n, rsx_dtype dtype, rsx_order orde
 			memset(out_place, 0, idx_bytes);
 		if (out_less)
 			memset(out_less, 0, idx_bytes);
-		if (out_equal) {
-			if (idx_bytes == 4)
-				*(uint32_t *)out_equal = 1;
-			else
-				*(uint64_t *)out_equal = 1;
-		}
+		if (out_equal)
+			put_index(out_equal, idx_bytes, 1);
 		info->sort.early_exit = 1;
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
+	// host buffers: the outputs staged in rdout as [place][less][equal]
 	void *const outs[3] = {out_place, out_less, out_equal};
-	if (is_device_ptr(src)) {
-		for (void *o : outs)
-			if (o && !is_device_ptr(o))
-				return fail(RSX_EINVAL, "rsx_sort_rankdata: src is a device pointer but an output is not");
-		RSX_TRY(rsx_sort_rankdata_device(src, n, dtype, order, out_place, out_less, out_equal, idx_bytes, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	// host buffers: the keys staged in recs[0] as rsx_sort_rank stages them, the outputs in [place][less][equal]
-	const size_t ipad = (n * idx_bytes + 255) & ~(size_t)255;
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->rdout.ensure(3 * ipad));
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	char *dout[3];
-	for (int i = 0; i < 3; ++i)
-		dout[i] = outs[i] ? (char *)c->rdout.p + (size_t)i * ipad : nullptr;
-	RSX_TRY(rsx_sort_rankdata_device(c->recs[0].p, n, dtype, order, dout[0], dout[1], dout[2], idx_bytes, nullptr, info));
-	for (int i = 0; i < 3; ++i)
-		if (outs[i])
-			HIP_TRY(hipMemcpyAsync(outs[i], dout[i], n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	const size_t esz[3] = {idx_bytes, idx_bytes, idx_bytes};
+	return staged_run(*c, "rsx_sort_rankdata", c->rdout, src, n, kb, idx_bytes, outs, esz, idx_slot_bytes(n, idx_bytes),
+	                  [&](const void *dsrc, void *const *o, size_t *count) {
+		                  count[0] = count[1] = count[2] = n;
+		                  return rsx_sort_rankdata_device(dsrc, n, dtype, order, o[0], o[1], o[2], idx_bytes, nullptr, info);
+	                  });
 }
 
 }  // extern "C"

@@ -1,140 +1,37 @@
 // rsx_unique_api.hpp: rsx_sort_unique[_device] -- the host driver (routes by bitmap, count table or sort + compaction over the kernels
-// of rsx_unique.hpp) and its entry points; part of librsx.so's host side, included by rsx.hip behind the routes and rsx_api.hpp.
+// of rsx_unique.hpp) and its entry points; part of librsx.so's host side, included by rsx.hip behind the routes, rsx_api.hpp and
+// rsx_keybits_api.hpp.
 #pragma once
 
 namespace {
 
 // ---- rsx_sort_unique_device: the distinct keys in order, by bitmap or count table where they fit (rsx_unique.hpp) ------
-// The sizes at which the ordinary sort would go without a histogram (blind_wanted's, without spending its back-off): there
-// a sample of the keys is looked at first, so that evenly spread keys never pay a histogram the sort would not have paid.
-template <typename KT> bool unique_sample_wanted(const Ctx &c, size_t n)
-{
-	if constexpr (sizeof(KT) < 4)
-		return false;
-	if (!blind_gate(c))
-		return false;
-	if (n < ((size_t)1 << 22) || n >= blind_keys_end<KT>())
-		return false;
-	size_t floor_keys = sizeof(KT) == 8 ? (size_t)9 << 19 : (size_t)15 << 19;
-	if (env().blind_min_log2)
-		floor_keys = (size_t)1 << env().blind_min_log2;
-	floor_keys = std::min(floor_keys, (size_t)1 << env().two_level_min_log2);
-	return n >= floor_keys;
-}
-
-inline u64 *unique_hdr(Ctx &c) { return (u64 *)c.urecs.p; }
-inline UniqueRec *unique_recs(Ctx &c) { return (UniqueRec *)((u64 *)c.urecs.p + 8); }
-
-// the number of distinct keys a read-out left in the header, once the stream is through
-inline int unique_total(Ctx &c, size_t *n_unique)
-{
-	u64 total = 0;
-	HIP_TRY(hipMemcpyAsync(&total, unique_hdr(c), sizeof total, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	*n_unique = (size_t)total;
-	return RSX_OK;
-}
-
-// the sorted array `in` compacted into `out`: count the heads per tile, scan, write (12 bytes per 4-byte key)
-template <typename KT>
-int unique_compact(Ctx &c, const KT *in, KT *out, size_t n, void *counts, size_t count_bytes, size_t *n_unique)
-{
-	const u64 tiles = ((u64)n + unique_heads_tile<KT>() - 1) / unique_heads_tile<KT>();
-	RSX_TRY(c.urecs.ensure(64 + (size_t)tiles * sizeof(UniqueRec)));
-	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 0>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c),
-	                   (KT *)nullptr, (void *)nullptr, 0u);
-	hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), tiles, unique_hdr(c));
-	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 1>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, in, (u64)n, unique_recs(c), out,
-	                   counts, (u32)count_bytes);
-	HIP_TRY(hipGetLastError());
-	return unique_total(c, n_unique);
-}
-
-// routes 1 and 2: every key sets its bit, the bitmap is read out in order.  *done = 0: no room for the bitmap.
-template <typename KT>
-int unique_bitmap(Ctx &c, const KT *src, KT *out, size_t n, KdfArgs<KT> ka, u64 vary, u32 vbits, const BitRuns &runs, size_t *n_unique,
-                  rsx_unique_info *info, int *done)
-{
-	*done = 0;
-	if constexpr (sizeof(KT) >= 2) {
-		const u64 words = std::max<u64>(UNIQUE_CHUNK_WORDS, ((u64)1 << vbits) / 32);   // (a multiple of the read-out's chunk)
-		const u64 chunks = words / UNIQUE_CHUNK_WORDS;
-		if (c.ubits.ensure((size_t)words * sizeof(u32)) != RSX_OK || c.urecs.ensure(64 + (size_t)chunks * sizeof(UniqueRec)) != RSX_OK)
-			return RSX_OK;   // (not an error: the caller takes the sort)
-		u32 *bitmap = (u32 *)c.ubits.p;
-		HIP_TRY(hipMemsetAsync(bitmap, 0, (size_t)words * sizeof(u32), c.stream));
-		// Two workgroups of 1024 threads fill a CU (2048 threads; 2 x 8 or 2 x 32 KiB of its 160 KiB of LDS); the 128 KiB form
-		// leaves room for one.  A workgroup should have at least four sweeps of its own to pay for zeroing and merging its bitmap.
-		const u64 nvec = (u64)n * sizeof(KT) / 16;
-		const u32 full = vbits > 18 && vbits <= 20 ? 256u : 512u;
-		const unsigned grid = (unsigned)std::max<u64>(1, std::min<u64>(full, nvec / 16384));
-		if (vbits <= 16)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 16>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else if (vbits <= 18)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 18>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else if (vbits <= 20)
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 20>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		else
-			hipLaunchKernelGGL((rsx_unique_mark_kernel<KT, 0>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, ka, runs, bitmap);
-		hipLaunchKernelGGL((rsx_unique_expand_kernel<KT, 0>), dim3((unsigned)chunks), dim3(256), 0, c.stream, (const u32 *)bitmap,
-		                   unique_recs(c), (KT *)nullptr, src, ka, runs, (KT)vary);
-		hipLaunchKernelGGL(rsx_unique_scan_kernel, dim3(1), dim3(1024), 0, c.stream, unique_recs(c), chunks, unique_hdr(c));
-		hipLaunchKernelGGL((rsx_unique_expand_kernel<KT, 1>), dim3((unsigned)chunks), dim3(256), 0, c.stream, (const u32 *)bitmap,
-		                   unique_recs(c), out, src, ka, runs, (KT)vary);
-		HIP_TRY(hipGetLastError());
-		info->route = vbits <= 20 ? RSX_UNIQUE_BITMAP_LDS : RSX_UNIQUE_BITMAP_GLOBAL;
-		info->table_bytes = (u64)words * sizeof(u32);
-		*done = 1;
-		return unique_total(c, n_unique);
-	}
-	return RSX_OK;
-}
-
 template <typename KT>
 int sort_unique_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order, void *counts, size_t count_bytes, void **result,
                        size_t *n_unique, rsx_unique_info *info)
 {
 	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
 	const u32 max_bits = env().unique_max_bits;
-	RSX_TRY(c.urecs.ensure(64 + 64 * sizeof(UniqueRec)));
-	bool have_plan = false, to_sort = false;
-	Plan plan{};
-	if (unique_sample_wanted<KT>(c, n)) {
-		// The sample can only PROVE that many bits vary (a bit that differs between two sampled keys differs among the keys):
-		// more than any bitmap or table here takes, and the keys go to the sort as if this entry point were rsx_sort_device.
-		const u64 init[2] = {0, ~0ull};
-		u64 got[2];
-		HIP_TRY(hipMemcpyAsync(unique_hdr(c), init, sizeof init, hipMemcpyHostToDevice, c.stream));
-		hipLaunchKernelGGL((rsx_unique_sample_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, ka, unique_hdr(c));
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(got, unique_hdr(c), sizeof got, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const u32 limit = !max_bits ? 0u : counts ? 8u : max_bits;   // (with counts: one kept column at most)
-		to_sort = (u32)__builtin_popcountll(got[0] ^ got[1]) > limit;
-	}
-	u64 vary = 0;
-	u32 vbits = 0;
-	if (!to_sort) {
-		RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, 0));
-		have_plan = true;
-		info_from_plan(&info->sort, plan);
-		vary = ((u64)plan.vary_hi << 32) | plan.vary_lo;
-		vbits = (u32)__builtin_popcountll(vary);
-		info->varying_bits = vbits;
-		if (plan.sorted)
-			info->sort.early_exit = 2;
-		if (vary == 0) {
+	KeyBits kb;
+	// (with counts: one kept column at most)
+	RSX_TRY(keybits_front<KT>(c, src, n, ka, !max_bits ? 0u : counts ? 8u : max_bits, &info->sort, &info->varying_bits, &kb));
+	const Plan &plan = kb.plan;
+	// a bitmap or table was read out into aux: how many keys that were
+	auto read_out = [&](uint32_t route, u64 table_bytes) {
+		info->route = route;
+		info->table_bytes = table_bytes;
+		*result = aux;
+		info->sort.result_in_aux = 1;
+		return unique_total(c, n_unique);
+	};
+	if (kb.planned) {
+		if (kb.vary == 0) {
 			// every key equal: the first one, n times
 			info->route = RSX_UNIQUE_TRIVIAL;
 			*result = src;
 			*n_unique = 1;
-			if (counts) {
-				const u64 c64 = n;
-				const u32 c32 = (u32)n;
-				HIP_TRY(hipMemcpyAsync(counts, count_bytes == 4 ? (const void *)&c32 : (const void *)&c64, count_bytes, hipMemcpyHostToDevice,
-				                       c.stream));
-				HIP_TRY(hipStreamSynchronize(c.stream));
-			}
+			if (counts)
+				RSX_TRY(put_index_device(counts, count_bytes, n, c.stream));
 			return RSX_OK;
 		}
 		if (max_bits && plan.ncols == 1) {
@@ -143,11 +40,7 @@ int sort_unique_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order,
 			hipLaunchKernelGGL((rsx_unique_table_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const u64 *)(c.ghist() + 256 * col),
 			                   (const u32 *)nullptr, 256u, (u64)n, 8 * col, (const KT *)src, ka, aux, counts, (u32)count_bytes, unique_hdr(c));
 			HIP_TRY(hipGetLastError());
-			info->route = RSX_UNIQUE_TABLE;
-			info->table_bytes = 256 * sizeof(u64);
-			*result = aux;
-			info->sort.result_in_aux = 1;
-			return unique_total(c, n_unique);
+			return read_out(RSX_UNIQUE_TABLE, 256 * sizeof(u64));
 		}
 		if constexpr (sizeof(KT) == 2) {
 			// 2-byte keys with counts: the joint table of both bytes (32-bit counters: below 2^32 keys; the kernel leaves sorted
@@ -161,28 +54,29 @@ int sort_unique_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order,
 				hipLaunchKernelGGL((rsx_unique_table_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const u64 *)nullptr, (const u32 *)jt,
 				                   65536u, (u64)n, 0u, (const KT *)src, ka, aux, counts, (u32)count_bytes, unique_hdr(c));
 				HIP_TRY(hipGetLastError());
-				info->route = RSX_UNIQUE_TABLE;
-				info->table_bytes = 65536 * sizeof(u32);
-				*result = aux;
-				info->sort.result_in_aux = 1;
-				return unique_total(c, n_unique);
+				return read_out(RSX_UNIQUE_TABLE, 65536 * sizeof(u32));
 			}
 		}
-		BitRuns runs;
-		if (!counts && vbits <= max_bits && bit_runs(vary, &runs)) {
-			int done = 0;
-			RSX_TRY(unique_bitmap<KT>(c, src, aux, n, ka, vary, vbits, runs, n_unique, info, &done));
-			if (done) {
-				*result = aux;
-				info->sort.result_in_aux = 1;
-				return RSX_OK;
+		if constexpr (sizeof(KT) >= 2) {
+			// routes 1 and 2: every key sets its bit, the bitmap is read out in order (no room for it: the sort)
+			BitRuns runs;
+			if (!counts && kb.vbits <= max_bits && bit_runs(kb.vary, &runs)) {
+				const BitmapShape s = bitmap_shape(kb.vbits);
+				int done = 0;
+				RSX_TRY(keybits_bitmap<KT>(c, src, n, ka, kb.vary, runs, s, &done));
+				if (done) {
+					hipLaunchKernelGGL((rsx_unique_expand_kernel<KT, 1>), dim3((unsigned)s.chunks), dim3(256), 0, c.stream, (const u32 *)c.ubits.p,
+					                   unique_recs(c), aux, (const KT *)src, ka, runs, (KT)kb.vary);
+					HIP_TRY(hipGetLastError());
+					return read_out(kb.vbits <= 20 ? RSX_UNIQUE_BITMAP_LDS : RSX_UNIQUE_BITMAP_GLOBAL, s.bytes);
+				}
 			}
 		}
 	}
 	// the ordinary sort (any route; every early exit), then one compaction of the sorted buffer into the other one
 	info->route = RSX_UNIQUE_SORT;
 	KT *in = src;
-	if (!(have_plan && plan.sorted)) {
+	if (!kb.sorted) {
 		void *res = nullptr;
 		rsx_info si;
 		info_clear(&si, dtype);
@@ -190,11 +84,16 @@ int sort_unique_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order,
 		info->sort = si;
 		in = (KT *)res;
 	}
+	// the sorted array `in` compacted into `out`: count the heads per tile, scan, write (12 bytes per 4-byte key)
 	KT *out = in == src ? aux : src;
-	RSX_TRY(unique_compact<KT>(c, in, out, n, counts, count_bytes, n_unique));
+	u64 tiles;
+	RSX_TRY(keybits_heads<KT>(c, (const KT *)in, n, &tiles));
+	hipLaunchKernelGGL((rsx_unique_heads_kernel<KT, 1>), dim3((unsigned)tiles), dim3(UNIQUE_HEADS_THREADS), 0, c.stream, (const KT *)in, (u64)n,
+	                   unique_recs(c), out, counts, (u32)count_bytes);
+	HIP_TRY(hipGetLastError());
 	*result = out;
 	info->sort.result_in_aux = out == aux;
-	return RSX_OK;
+	return unique_total(c, n_unique);
 }
 
 }  // namespace
@@ -231,11 +130,7 @@ int rsx_sort_unique_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, 
 	RSX_TRY(refuse_capture(stream, "rsx_sort_unique_device", "the call waits for the number of distinct keys"));
 	if (n == 1) {
 		// (one key, once: the only small case that has to write device memory)
-		const u64 one64 = 1;
-		const u32 one32 = 1;
-		HIP_TRY(hipMemcpyAsync(d_counts, count_bytes == 4 ? (const void *)&one32 : (const void *)&one64, count_bytes, hipMemcpyHostToDevice,
-		                       (hipStream_t)stream));
-		HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+		RSX_TRY(put_index_device(d_counts, count_bytes, 1, (hipStream_t)stream));
 		*result = d_src;
 		*n_unique = 1;
 		info->sort.early_exit = 1;
@@ -261,10 +156,7 @@ int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order o
 		return RSX_OK;
 	}
 	if (one_on_host(n, src)) {
-		if (count_bytes == 4)
-			*(uint32_t *)counts = 1;
-		else
-			*(uint64_t *)counts = 1;
+		put_index(counts, count_bytes, 1);
 		*result = src;
 		*n_unique = 1;
 		info->sort.early_exit = 1;
