@@ -6,6 +6,9 @@
 // scatter pass per kept column, ping-ponging two buffers -> "returned pointer".
 // There is deliberately no CPU path here: if HIP cannot give us a gfx950
 // device, every entry point fails with RSX_ENODEVICE.
+// This file holds the passes themselves -- launch_hist, plan_phase, scatter_pass and their kin -- and the list of the parts
+// that make up the host side (one translation unit: the kernel instantiations are shared); the drivers of the plain sorts are in
+// rsx_sort_plain.hpp and rsx_sort_async.hpp, their entry points in rsx_plain_api.hpp, every feature in a file of its own.
 #include "../../include/rsx.h"
 #include "rsx_kernels.hpp"
 #include "rsx_scatter2.hpp"
@@ -43,6 +46,7 @@ using namespace rsx;
 
 #include "rsx_env.hpp"          // the RSX_* switches
 #include "rsx_seg_layout.hpp"   // SegLayout, SlotParts: where the segmented routes' control block and level-1 slots lie
+#include "rsx_ws_layout.hpp"    // WsLayout: where the parts of a caller-owned workspace lie
 #include "rsx_ctx.hpp"          // the error convention, DevBuf, Ctx, profiling, get_ctx
 #include "rsx_route_levels.hpp" // MSB passes and leaves behind a histogram: the control block, the leaves, one and two levels
 #include "rsx_route_blind.hpp"  // ... and without one: gates, sizes, blind_enqueue / pairs_blind_enqueue and their blocking sorts
@@ -419,889 +423,12 @@ int scatter_pass_to(Ctx &c, const KT *kin, void *kout, u32 out_bytes, const VT *
 	return fail(RSX_EINVAL, "scatter_pass_to: %u-byte keys out of %zu-byte keys", out_bytes, sizeof(KT));
 }
 
-// ---- 8-byte keys by (bit length, mantissa) digits: rsx_logroute.hpp ----------------------------------------------------------
-// Tried where the sorts without a histogram do not go (their sample said no, or they are backing off): the route's own sample
-// says at once whether it is worth the histogram; everything behind it is device-scheduled and the verdict is read once.
-template <typename KT> bool log_wanted(Ctx &c, size_t n, const KT *src, const KT *aux)
-{
-	if constexpr (sizeof(KT) != 8)
-		return false;
-	if (env().no_log || !hybrid_enabled() || !c.fast || capture_armed() || verify_mode() || c.small.external || env().no_speculation)
-		return false;
-	// from 24 Mi keys: Zipf-like keys (BASELINE.json's cfg 3 (iv)) against one pass per kept column, one box, tools/log_sizes.py --
-	// 16 Mi 0.49 against 0.43 ms (65536 leaf workgroups are a fixed 0.24 ms), 24 Mi 0.55 against 0.61, 32 Mi 0.63 against 0.78,
-	// 64 Mi 0.89 against 1.46, 128 Mi 1.43 against 2.65, 256 Mi 2.46 against 5.09 (profiles/r06/log_sizes.txt)
-	const size_t floor_keys = env().log_min_log2 ? (size_t)1 << env().log_min_log2 : (size_t)3 << 23;
-	// (up to 2^29 + 2^25 keys: a level-1 bucket must fit 256 leaves -- of 5120 values up to 2^28 + 2^24 keys, of 10240 beyond; the
-	// heaviest digits of Zipf-like keys hold 1 / 256 of the array -- and larger arrays would pay for the histogram before the plan
-	// kernel says no)
-	if (n < floor_keys || n > ((size_t)17 << 25))
-		return false;
-	if (((((uintptr_t)src) & 15) | (((uintptr_t)aux) & 63)) != 0)   // (16-byte loads of the input, 64-byte atoms into aux)
-		return false;
-	// an attempt that its sample refuses costs a memset, the sample and eight empty launches -- 65 us, 7 % of a sort of 24 Mi keys --,
-	// a lost one the histogram and a pass or two: after either the next 1, 3, 7 .. 31 sorts of the context do not ask
-	// (tools/log_overhead.py; rsx_reload_env() forgets, as for the sorts without a histogram)
-	blind_refresh(c);
-	if (c.log_skip) {
-		--c.log_skip;
-		return false;
-	}
-	return true;
-}
+}  // namespace
 
-template <typename KT>
-int sort_keys_log(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, KT **result, rsx_info *info, int *done)
-{
-	*done = 0;
-	if constexpr (sizeof(KT) == 8) {
-		typedef LogP2Cfg P2;
-		const size_t tiles_cap = n / P2::TILE + 257;
-		const size_t cur2_off = sizeof(LogCtl), tabs_off = cur2_off + 2 * 65536 * sizeof(u32);
-		const size_t tiles_off = (tabs_off + sizeof(LogTabs) + 255) & ~(size_t)255;
-		const size_t zero_bytes = tabs_off + offsetof(LogTabs, offs_small);
-		const size_t l2_cap = n + n / 8 + (size_t)65536 * 700;   // level-2 slots: values (rsx_log_plan_kernel checks the exact sum)
-		if (c.logb.ensure(tiles_off + tiles_cap * sizeof(LogTile)) != RSX_OK ||
-		    c.logslots.ensure((l2_cap + P2::TILE + 64) * sizeof(u32)) != RSX_OK) {
-			(void)hipGetLastError();
-			return RSX_OK;   // (no room: the ordinary path)
-		}
-		if (!c.host_logctl)
-			HIP_TRY(hipHostMalloc((void **)&c.host_logctl, sizeof(LogCtl), hipHostMallocDefault));
-		if (!c.log_ev)
-			HIP_TRY(hipEventCreateWithFlags(&c.log_ev, hipEventDisableTiming));
-		LogCtl *ctl = (LogCtl *)c.logb.p;
-		u32 *cur2 = (u32 *)((char *)c.logb.p + cur2_off);
-		LogTabs *tabs = (LogTabs *)((char *)c.logb.p + tabs_off);
-		LogTile *tiles = (LogTile *)((char *)c.logb.p + tiles_off);
-		u32 *slots = (u32 *)c.logslots.p;
-		const size_t pmark = prof_mark();
-		HIP_TRY(hipMemsetAsync(c.logb.p, 0, zero_bytes, c.stream));
-		// the leaves' shape: 5120 values per slot (five workgroups of 256 threads per CU) up to 2^28 + 2^24 keys, 10240 beyond
-		const bool big_leaves = n > ((size_t)17 << 24) || env().log_leaf_big;
-		hipLaunchKernelGGL((rsx_log_sample_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, ka, ctl,
-		                   big_leaves ? LOG_LEAF_CAP_BIG : LOG_LEAF_CAP);
-		{
-			ProfScope prof(0, (u64)n * sizeof(KT), c.stream);
-			hipLaunchKernelGGL((rsx_log_hist_kernel<KT>), dim3(512), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, ka, ctl, tabs);
-		}
-		hipLaunchKernelGGL(rsx_log_plan_kernel, dim3(1), dim3(1024), 0, c.stream, ctl, tabs, tiles, (u64)n, (u32)n, (u32)l2_cap,
-		                   (u32)tiles_cap, (u32)P2::TILE, (u32)P2::GRID, (Plan *)nullptr, c.dev_host_plan);
-		{
-			ProfScope prof(1, 0, c.stream);
-			hipLaunchKernelGGL((rsx_log_pass1_kernel<KT>), dim3(256), dim3(LogP1Cfg::BLOCK), 0, c.stream, (const KT *)src, (u64)n, aux,
-			                   ctl, tabs, ka);
-		}
-		{
-			ProfScope prof(3, 0, c.stream);
-			hipLaunchKernelGGL((rsx_log_pass2_kernel<KT>), dim3(P2::GRID), dim3(P2::BLOCK), 0, c.stream, (const KT *)aux, slots,
-			                   (const LogTile *)tiles, ctl, (const LogTabs *)tabs, cur2, (u32)l2_cap, ka);
-		}
-		{
-			ProfScope prof(2, 0, c.stream);
-			hipLaunchKernelGGL((rsx_log_fill_kernel<KT>), dim3(2048), dim3(LOG_FILL_BLOCK), 0, c.stream, src, aux, (const LogCtl *)ctl,
-			                   (const LogTabs *)tabs, ka);
-			if (big_leaves)
-				hipLaunchKernelGGL((rsx_log_leaf_kernel<KT, LogLeafCfgBig>), dim3(65536), dim3(LogLeafCfgBig::BLOCK), 0, c.stream, src, aux,
-				                   (const u32 *)slots, (const LogCtl *)ctl, (const LogTabs *)tabs, (const u32 *)cur2, ka, 0u, 256u);
-			else
-				hipLaunchKernelGGL((rsx_log_leaf_kernel<KT, LogLeafCfg>), dim3(65536), dim3(LogLeafCfg::BLOCK), 0, c.stream, src, aux,
-				                   (const u32 *)slots, (const LogCtl *)ctl, (const LogTabs *)tabs, (const u32 *)cur2, ka, 0u, 256u);
-		}
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipMemcpyAsync(c.host_logctl, ctl, sizeof(LogCtl), hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipEventRecord(c.log_ev, c.stream));
-		HIP_TRY(hipEventSynchronize(c.log_ev));
-		const LogCtl h = *c.host_logctl;
-		if (!h.go || h.fail || (!h.ok && !h.sorted)) {
-			prof_called_off(pmark, c.stream);   // (not this route's keys, or an attempt that was lost: the ordinary path)
-			c.log_backoff = std::min<u32>(2 * c.log_backoff + 1, 31);
-			c.log_skip = c.log_backoff;
-			return RSX_OK;
-		}
-		c.log_backoff = 0;
-		const Plan plan = *c.host_plan;
-		info_from_plan(info, plan);
-		*done = 1;
-		if (h.sorted) {   // radix_sort.hpp:60-62
-			prof_called_off(pmark, c.stream, 1);
-			prof_called_off(pmark, c.stream, 2);
-			prof_called_off(pmark, c.stream, 3);
-			if (info) {
-				info->early_exit = 2;
-				info->ncols = 0;
-			}
-			*result = src;
-			return RSX_OK;
-		}
-		const u64 nsmall = h.nsmall, nbig = n - nsmall;
-		prof_rebook(pmark, c.stream, 1, (u64)n * sizeof(KT) + nbig * sizeof(KT));
-		prof_rebook(pmark, c.stream, 3, nbig * (sizeof(KT) + 4));
-		prof_rebook(pmark, c.stream, 2, nbig * (4 + sizeof(KT)) + nsmall * sizeof(KT));
-		KT *final = (plan.ncols & 1) ? aux : src;   // radix_sort.hpp:92
-		*result = final;
-		if (info) {
-			info->result_in_aux = final == aux;
-			info->hybrid = 6u;
-		}
-	}
-	return RSX_OK;
-}
+#include "rsx_sort_plain.hpp"  // the blocking drivers: sort_keys_device, sort_pairs_device, sort_rank_device; the RSX_VERIFY=2 bracket
+#include "rsx_sort_async.hpp"  // the device-scheduled ones: sort_*_inplace_async and the skeleton they share
 
-// ---- keys only -------------------------------------------------------------------
-template <typename KT>
-int sort_keys_device_impl(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order, void **result, rsx_info *info);
-
-// RSX_VERIFY=2: the sort as it always runs (speculation, leaves, slack slots ...), bracketed by rsx_checksum_kernel on the
-// input and on the result: not sorted, or not the same keys -> RSX_EVERIFY.  (RSX_VERIFY=1 re-ranks a tile of every PASS and
-// therefore keeps to the pass kernels; this one is blind to where an error came from but covers every route.)
-template <typename KT>
-int sort_keys_device(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order, void **result, rsx_info *info)
-{
-	if (!env().verify_whole)
-		return sort_keys_device_impl<KT>(c, src, aux, n, dtype, order, result, info);
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	RSX_TRY(c.vsum.ensure(6 * sizeof(u64)));
-	u64 *vs = (u64 *)c.vsum.p;
-	HIP_TRY(hipMemsetAsync(vs, 0, 6 * sizeof(u64), c.stream));
-	hipLaunchKernelGGL((rsx_checksum_kernel<KT>), dim3(2048), dim3(256), 0, c.stream, (const KT *)src, (u64)n, ka, vs);
-	HIP_TRY(hipGetLastError());
-	RSX_TRY(sort_keys_device_impl<KT>(c, src, aux, n, dtype, order, result, info));
-	hipLaunchKernelGGL((rsx_checksum_kernel<KT>), dim3(2048), dim3(256), 0, c.stream, (const KT *)*result, (u64)n, ka, vs + 3);
-	HIP_TRY(hipGetLastError());
-	u64 h[6];
-	HIP_TRY(hipMemcpyAsync(h, vs, sizeof h, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	if (env().verify_inject)   // (test hook: the failure report end to end)
-		h[5] ^= 1;
-	if (h[3] != 0 || h[1] != h[4] || h[2] != h[5])
-		return fail(RSX_EVERIFY, "RSX_VERIFY=2: the result of a sort of %zu keys (route %u) is %s: %llu descents, key sum %s, key mix %s",
-		            n, info ? info->hybrid : 0u, h[3] ? "not sorted" : "not a permutation of the input", (unsigned long long)h[3],
-		            h[1] == h[4] ? "kept" : "changed", h[2] == h[5] ? "kept" : "changed");
-	return RSX_OK;
-}
-
-template <typename KT>
-int sort_keys_device_impl(Ctx &c, KT *src, KT *aux, size_t n, int dtype, int order, void **result, rsx_info *info)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (c.fast && n * sizeof(KT) <= SMALL_SORT_BYTES && !env().no_small_sort && !capture_armed()) {
-		// the whole sort in one workgroup and one launch (rsx_small.hpp)
-		ProfScope prof(1, (u64)n * 2 * sizeof(KT), c.stream);
-		hipLaunchKernelGGL((rsx_small_sort_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, src, aux, (u32)n, ka, c.dev_host_plan);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const Plan p = *c.host_plan;
-		info_from_plan(info, p);
-		if (info && p.sorted)
-			info->early_exit = 2;
-		*result = (p.ncols & 1) ? aux : src;     // radix_sort.hpp:92 (sorted input: no column, src)
-		if (info)
-			info->result_in_aux = *result == aux;
-		return RSX_OK;
-	}
-	Plan plan;
-	if constexpr (sizeof(KT) == 1) {
-		// 1-byte keys: at most one column, so the sorted array is the histogram written out (rsx_fill_runs_kernel) -- a read
-		// and a write of the keys instead of a read, a read and a scatter
-		if (!env().no_fill_runs && (((uintptr_t)aux) & 15) == 0) {
-			RSX_TRY(plan_phase<KT>(c, src, n, ka, nullptr, 0));
-			const unsigned blocks = (unsigned)std::min<u64>((n / 16 + 255) / 256 + 1, 8192);
-			hipLaunchKernelGGL((rsx_fill_runs_kernel<KT>), dim3(blocks), dim3(256), 0, c.stream, aux, (u64)n, (const u64 *)c.ghist(),
-			                   (const KT *)src, ka, (const Plan *)c.plan());
-			HIP_TRY(hipGetLastError());
-			RSX_TRY(plan_wait(c, &plan));
-			info_from_plan(info, plan);
-			RSX_TRY(capture_hist(c, n, sizeof(KT)));
-			if (plan.sorted)                     // radix_sort.hpp:60-62
-				return finish_sorted(info, result, src);
-			*result = aux;                       // one pass: radix_sort.hpp:92
-			if (info)
-				info->result_in_aux = 1;
-			return RSX_OK;
-		}
-	}
-	if constexpr (sizeof(KT) >= 4) {
-		// large arrays: two MSB passes and leaves without the histogram, where a sample of the keys allows it (rsx_hybrid.hpp)
-		if (blind_wanted<KT>(c, n)) {
-			int done = 0;
-			KT *res = nullptr;
-			RSX_TRY(sort_keys_blind<KT>(c, src, aux, n, ka, &res, info, &done));
-			if (done) {
-				*result = res;
-				return RSX_OK;
-			}
-		}
-	}
-	if constexpr (sizeof(KT) == 8) {
-		// 8-byte keys the byte columns do not spread (heavy-tailed magnitudes): digits of (bit length, mantissa), rsx_logroute.hpp
-		if (log_wanted<KT>(c, n, src, aux)) {
-			int done = 0;
-			KT *res = nullptr;
-			RSX_TRY(sort_keys_log<KT>(c, src, aux, n, ka, &res, info, &done));
-			if (done) {
-				*result = res;
-				return RSX_OK;
-			}
-		}
-	}
-	// The first pass is enqueued before the host knows the plan (it reads the device's copy and does nothing on
-	// sorted input): the host's wait for the plan, 20-25 us of idle GPU otherwise, hides behind it.
-	const bool spec = c.fast && !env().no_speculation && !verify_mode();
-	// with the fast kernel every pass has its own region of status words, all zeroed together with the histogram
-	const size_t status_total = c.fast ? status_bytes<KT, NoVal>(n) * sizeof(KT) : 0;
-	if constexpr (sizeof(KT) == 2) {
-		// 2-byte keys, large arrays: one 16-bit digit.  The sorted array is written from the joint histogram of the two bytes
-		// (rsx_joint16_kernel ... rsx_fill16_kernel) into `src` -- where two passes end (radix_sort.hpp:92) --, from one
-		// byte's histogram into `aux` if only one column is kept; the device-side plan decides, no kernel scatters.
-		// (below 2^32 keys: the joint table counts in 32 bits, and one 16-bit value may occur n times; larger arrays take the
-		// two scatter passes, whose status words are 64-bit from 2^30 keys on -- counter width by n, radix_sort.hpp:102-114)
-		if (!env().no_fill_runs && n >= ((size_t)1 << 20) && n < ((size_t)1 << 32) && ((((uintptr_t)aux) | ((uintptr_t)src)) & 15) == 0) {
-			RSX_TRY(c.joint.ensure(65536 * sizeof(u32) + 65537 * sizeof(u64) + 8));
-			u32 *jt = (u32 *)c.joint.p;
-			u64 *offs = (u64 *)((char *)c.joint.p + 65536 * sizeof(u32));
-			HIP_TRY(hipMemsetAsync(jt, 0, 65536 * sizeof(u32), c.stream));
-			RSX_TRY(plan_phase<KT>(c, src, n, ka, nullptr, 0));
-			hipLaunchKernelGGL(rsx_joint16_kernel, dim3(512), dim3(1024), 0, c.stream, (const uint16_t *)src, (u64)n, ka, jt,
-			                   (const Plan *)c.plan());
-			hipLaunchKernelGGL(rsx_joint16_scan_kernel, dim3(1), dim3(1024), 0, c.stream, (const u32 *)jt, offs, (u64)n,
-			                   (const Plan *)c.plan());
-			const unsigned blocks = (unsigned)std::min<u64>((n / 8 + 255) / 256 + 1, 8192);
-			hipLaunchKernelGGL(rsx_fill16_kernel, dim3(blocks), dim3(256), 0, c.stream, (uint16_t *)src, (u64)n, (const u64 *)offs, ka,
-			                   (const Plan *)c.plan());
-			hipLaunchKernelGGL((rsx_fill_runs_kernel<KT>), dim3(blocks), dim3(256), 0, c.stream, aux, (u64)n, (const u64 *)c.ghist(),
-			                   (const KT *)src, ka, (const Plan *)c.plan());
-			HIP_TRY(hipGetLastError());
-			RSX_TRY(plan_wait(c, &plan));
-			info_from_plan(info, plan);
-			RSX_TRY(capture_hist(c, n, sizeof(KT)));
-			if (plan.sorted)                     // radix_sort.hpp:60-62
-				return finish_sorted(info, result, src);
-			*result = plan.ncols == 1 ? aux : src;
-			if (info)
-				info->result_in_aux = plan.ncols == 1;
-			return RSX_OK;
-		}
-	}
-	// One kept column (keys that differ in one byte only): the sorted array is written from the histogram instead of
-	// scattered (rsx_fill_runs_kernel).  With a speculative first pass both kernels are enqueued and the device-side plan
-	// decides which of them works, which costs an empty launch (3 us) in the usual case: only from 16 Mi keys on, where that is 1 %.
-	const bool fill_one = sizeof(KT) > 1 && !env().no_fill_runs && (((uintptr_t)aux) & 15) == 0 && (!spec || n >= ((size_t)1 << 24));
-	auto launch_fill = [&]() {
-		const unsigned blocks = (unsigned)std::min<u64>((n * sizeof(KT) / 16 + 255) / 256 + 1, 8192);
-		hipLaunchKernelGGL((rsx_fill_runs_kernel<KT>), dim3(blocks), dim3(256), 0, c.stream, aux, (u64)n, (const u64 *)c.ghist(),
-		                   (const KT *)src, ka, (const Plan *)c.plan());
-		return hipGetLastError();
-	};
-	u32 spec_leaves = 0;
-	bool self_planned = false;
-	const size_t pmark = prof_mark();
-	if (spec) {
-		// (the device may choose one MSB pass and leaves, rsx_hybrid.hpp: pass 0 then goes by the highest kept column)
-		const HybCaps caps = capture_armed() ? HybCaps{0, 0, 0, 0} : hybrid_caps<KT>(n);
-		// Mid-size arrays: pass 0 derives the plan itself (SCATTER_SELF_PLAN, rsx_scatter2.hpp) -- no plan launch.  (Not
-		// with a caller's histogram: its counts are read back from the scanned offsets a plan kernel leaves.)
-		self_planned = sizeof(KT) >= 4 && caps.cap1 != 0 && n <= ((size_t)1 << 23) && !fill_one && !env().no_self_plan;
-		RSX_TRY(plan_phase<KT>(c, src, n, ka, nullptr, status_total, caps, true, &self_planned));
-		u32 flags0 = fill_one ? (u32)SCATTER_ONE_COL_FILLED : 0u;
-		if (self_planned) {
-			flags0 |= SCATTER_SELF_PLAN;
-			c.pass_sp = SelfPlanArgs{(const u32 *)c.unsorted(), c.plan(), c.dev_host_plan, (u64 *)c.gscan.p, caps};
-		}
-		const int rc0 = scatter_pass<KT, NoVal>(c, src, aux, nullptr, nullptr, n, 0, c.ghist(), ka, flags0, c.plan(), 0);
-		c.pass_sp = SelfPlanArgs{nullptr, nullptr, nullptr, nullptr, HybCaps{0, 0, 0, 0}};
-		RSX_TRY(rc0);
-		if (self_planned) {   // the plan is pass 0's workgroup 0's now
-			if (!c.plan_ev)
-				HIP_TRY(hipEventCreateWithFlags(&c.plan_ev, hipEventDisableTiming));
-			HIP_TRY(hipEventRecord(c.plan_ev, c.stream));
-		}
-		if (fill_one)
-			HIP_TRY(launch_fill());
-		if constexpr (sizeof(KT) >= 4) {
-			// one MSB pass and leaves, if the device-side plan says so: enqueued now, so that nothing waits for the host
-			// (the large shape only where even spread keys would come near the small one's capacity; else after the wait)
-			if (caps.cap1 && n <= (size_t)256 * caps.cap1) {
-				spec_leaves = n / 256 > (size_t)LeafShapes<KT>::Small::CAP / 2 ? (LeafShapes<KT>::HAS_MEDIUM ? 7u : 3u) : 1u;
-				RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_ONE_LEVEL, spec_leaves, self_planned ? (const u64 *)c.gscan.p : nullptr));
-			}
-		}
-		RSX_TRY(plan_wait(c, &plan));
-	} else {
-		RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, status_total));
-	}
-	info_from_plan(info, plan);
-	RSX_TRY(capture_hist(c, n, sizeof(KT)));
-	// (the profile books what the device chose: leaves enqueued for a plan that did not come, a pass 0 that found the input sorted)
-	if (spec_leaves && (plan.sorted || plan.hyb != HYB_ONE_LEVEL))
-		prof_called_off(pmark, c.stream, 2);
-	if (spec && plan.sorted)
-		prof_called_off(pmark, c.stream, 1);
-	if (plan.sorted)                         // radix_sort.hpp:60-62
-		return finish_sorted(info, result, src);
-	if (fill_one && plan.ncols == 1) {
-		if (!spec)
-			HIP_TRY(launch_fill());
-		*result = aux;                       // one pass: radix_sort.hpp:92
-		if (info)
-			info->result_in_aux = 1;
-		return RSX_OK;
-	}
-	if constexpr (sizeof(KT) >= 4) {
-		if (plan.hyb == HYB_ONE_LEVEL || plan.hyb == HYB_TWO_LEVEL) {
-			// pass 0 went by the highest kept column; the leaves put the result where an LSB-first sort of plan.ncols passes ends
-			KT *final = (plan.ncols & 1) ? aux : src;
-			u32 how = 1;
-			if (plan.hyb == HYB_TWO_LEVEL) {
-				RSX_TRY(sort_keys_two_level<KT>(c, src, aux, n, ka, plan, &final, &how));
-			} else {
-				// one level: the leaves are on their way, unless they need a shape that was not enqueued
-				const u32 need = LeafShapes<KT>::shape_for(plan.max1);
-				if (!(spec_leaves & need))
-					RSX_TRY(launch_leaves<KT>(c, src, aux, n, ka, HYB_ONE_LEVEL, need, self_planned ? (const u64 *)c.gscan.p : nullptr));
-			}
-			*result = final;                     // radix_sort.hpp:92
-			if (info) {
-				info->result_in_aux = final == aux;
-				info->hybrid = how;
-			}
-			return RSX_OK;
-		}
-	}
-	if (self_planned && plan.ncols > 1) {
-		// one pass per kept column after a self-planned pass 0: the other columns' scans (and the hot digits) are made now
-		hipLaunchKernelGGL((rsx_plan_all_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, (const KT *)src, (u64)n, c.ghist(), ka, c.kept(),
-		                   c.hotd(), (const u32 *)c.unsorted(), c.plan(), c.dev_host_plan, HybCaps{0, 0, 0, 0});
-		HIP_TRY(hipGetLastError());
-	}
-	KT *cur = src, *oth = aux;
-	if (spec)
-		std::swap(cur, oth);                 // pass 0 is on its way
-	for (u32 i = spec ? 1 : 0; i < plan.ncols; ++i) {   // radix_sort.hpp:83-90
-		const u32 col = plan.cols[i];
-		RSX_TRY((scatter_pass<KT, NoVal>(c, cur, oth, nullptr, nullptr, n, 8 * col, c.ghist() + 256 * col, ka,
-		                                 hot_flags(plan.hot, col), nullptr, c.fast ? (int)i : -1)));
-		std::swap(cur, oth);
-	}
-	*result = cur;                           // radix_sort.hpp:92
-	if (info)
-		info->result_in_aux = cur == aux;
-	return RSX_OK;
-}
-
-// ---- keys only, no host synchronisation: every pass is device-scheduled, the result always ends in `buf` ------------
-template <typename KT>
-int sort_keys_inplace_async(Ctx &c, KT *buf, KT *scratch, size_t n, int dtype, int order)
-{
-	if (!c.fast)
-		return fail(RSX_EHIP, "rsx_sort_inplace_async needs the fast scatter kernel (the device self-check failed on this device)");
-	c.async_tried_blind = false;   // (rsx_async_route reports THIS call: set again below if an attempt is enqueued)
-	c.async_small = false;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (n * sizeof(KT) <= SMALL_SORT_BYTES) {
-		hipLaunchKernelGGL((rsx_small_sort_kernel<KT>), dim3(1), dim3(1024), 0, c.stream, buf, scratch, (u32)n, ka, c.dev_host_plan, true);
-		HIP_TRY(hipGetLastError());
-		c.async_small = true;
-		return RSX_OK;
-	}
-	const size_t status_total = status_bytes<KT, NoVal>(n) * sizeof(KT);
-	// The routes of the blocking sort (rsx_hybrid.hpp), chosen on the device with nobody to read a verdict back:
-	//  * arrays the sort without a histogram is for: the whole attempt is enqueued first -- sample, two MSB passes
-	//    into slots, leaves -- and what follows (histogram, plan, one pass per kept column) looks at the attempt's verdict,
-	//    SegCtl::mode, and does nothing if the keys are sorted by then; an attempt that is called off has only read `buf`.
-	//    (The host never learns how an attempt went: a context's back-off after a LOST attempt -- one that passed the sample and
-	//    then overflowed a slot -- is kept on the device, SegCtl::boff_skip.  An attempt the sample turns away costs a sample kernel
-	//    and a few empty launches, one that goes through the empty launches of the histogram-first kernels.)
-	//  * mid-size arrays: one MSB pass and leaves where the device-side plan says so (Plan::hyb) -- pass 0 then goes by the
-	//    highest kept column, the leaf launches behind it do nothing otherwise, and the passes 1 .. do nothing if they do.
-	// A caller-owned workspace (rsx_sort_inplace_async_ws) makes the attempt if it was sized for the slots (rsx_workspace_bytes_fast).
-	HybCaps caps{0, 0, 0, 0};
-	int blind = 0;
-	ProfAsyncVerdict pverdict(c.stream);   // (rsx_profile books what the device chose: the attempt's launches or the ones behind it)
-	if constexpr (sizeof(KT) >= 4) {
-		if (hybrid_enabled() && !verify_mode() && !env().no_speculation) {
-			caps = hybrid_caps<KT>(n);
-			caps.cap2 = caps.min_cols2 = 0;
-			if (async_blind_ok<KT>(c, n))
-				RSX_TRY(blind_enqueue<KT>(c, buf, scratch, n, ka, &blind));
-		}
-	}
-	if (blind)
-		pverdict.attempt_enqueued(SegView(c).ctl());
-	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
-	c.async_tried_blind = blind != 0;
-	int rc = plan_phase<KT>(c, buf, n, ka, nullptr, status_total, caps);
-	for (u32 i = 0; i < sizeof(KT) && rc == RSX_OK; ++i)   // pass i = the i-th kept column, if there is one (radix_sort.hpp:83-90)
-		rc = scatter_pass<KT, NoVal>(c, buf, scratch, nullptr, nullptr, n, 0, c.ghist(), ka, 0, c.plan(), (int)i, i);
-	c.pass_gate = nullptr;
-	RSX_TRY(rc);
-	if constexpr (sizeof(KT) >= 4) {
-		if (caps.cap1 && n <= (size_t)256 * caps.cap1) {
-			// (every shape: which one the largest bucket needs is only known on the device, and each does nothing unless the
-			// plan's largest bucket is its size -- keys with 64 values in their top byte fill buckets four times the mean)
-			const u32 shapes = LeafShapes<KT>::HAS_MEDIUM ? 7u : 3u;
-			RSX_TRY(launch_leaves<KT>(c, buf, scratch, n, ka, HYB_ONE_LEVEL, shapes));
-		}
-	}
-	pverdict.gated_enqueued();
-	// an odd number of kept columns leaves the result in `scratch` (radix_sort.hpp:92): bring it home
-	hipLaunchKernelGGL(rsx_copy_if_odd_kernel, dim3(2048), dim3(256), 0, c.stream, (unsigned char *)buf, (const unsigned char *)scratch,
-	                   (u64)n * sizeof(KT), (const Plan *)c.plan());
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// ---- key + payload, no host synchronisation: as sort_keys_inplace_async, the result always in (k, v) -----------------------
-template <typename KT, typename VT>
-int sort_pairs_inplace_async(Ctx &c, KT *k, KT *ks, VT *v, VT *vs, size_t n, int dtype, int order)
-{
-	if (!c.fast)
-		return fail(RSX_EHIP, "rsx_sort_pairs_inplace_async needs the fast scatter kernel (the device self-check failed on this device)");
-	c.async_tried_blind = false;   // (rsx_async_route reports THIS call: set again below if an attempt is enqueued)
-	c.async_small = false;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (n * 2 * (sizeof(KT) + sizeof(VT)) <= SMALL_PAIR_BYTES) {
-		hipLaunchKernelGGL((rsx_small_pairs_kernel<KT, VT, false>), dim3(1), dim3(1024), 0, c.stream, (const KT *)k, ks, v, vs, (u32)n,
-		                   ka, c.dev_host_plan, true);
-		HIP_TRY(hipGetLastError());
-		c.async_small = true;
-		return RSX_OK;
-	}
-	const size_t status_total = status_bytes<KT, VT>(n) * sizeof(KT);
-	// as sort_keys_inplace_async: the attempt without a histogram first (4-byte keys and payloads, 16 Mi .. 2^28 pairs: two MSB
-	// passes into slots and the pairs' leaves, which write (k, v) -- an attempt that is called off has only read them), the
-	// histogram-first kernels behind it gated on its verdict
-	int blind = 0;
-	ProfAsyncVerdict pverdict(c.stream);
-	if constexpr (sizeof(KT) == 4 && sizeof(VT) == 4) {
-		if (async_pairs_blind_ok<KT>(c, n, sizeof(VT)))
-			RSX_TRY((pairs_blind_enqueue<KT, VT>(c, k, v, k, v, n, ka, &blind, ks, vs)));
-	}
-	if (blind)
-		pverdict.attempt_enqueued(SegView(c).ctl());
-	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
-	c.async_tried_blind = blind != 0;
-	int rc = plan_phase<KT>(c, k, n, ka, nullptr, status_total);
-	for (u32 i = 0; i < sizeof(KT) && rc == RSX_OK; ++i)
-		rc = scatter_pass<KT, VT>(c, k, ks, v, vs, n, 0, c.ghist(), ka, 0, c.plan(), (int)i, i);
-	c.pass_gate = nullptr;
-	RSX_TRY(rc);
-	pverdict.gated_enqueued();
-	hipLaunchKernelGGL(rsx_copy_if_odd_kernel, dim3(2048), dim3(256), 0, c.stream, (unsigned char *)k, (const unsigned char *)ks,
-	                   (u64)n * sizeof(KT), (const Plan *)c.plan());
-	hipLaunchKernelGGL(rsx_copy_if_odd_kernel, dim3(2048), dim3(256), 0, c.stream, (unsigned char *)v, (const unsigned char *)vs,
-	                   (u64)n * sizeof(VT), (const Plan *)c.plan());
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
-
-// ---- key + payload -----------------------------------------------------------------
-template <typename KT, typename VT>
-int sort_pairs_device_impl(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int dtype, int order, rsx_info *info);
-
-// RSX_VERIFY=2 (as for keys-only sorts): the sort on its usual route, bracketed by checksums of the PAIRS: the result's keys
-// must not descend and its key sum and pair mix must be the input's.
-template <typename KT, typename VT>
-int sort_pairs_device(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int dtype, int order, rsx_info *info)
-{
-	if (!env().verify_whole)
-		return sort_pairs_device_impl<KT, VT>(c, k0, k1, v0, v1, n, dtype, order, info);
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	RSX_TRY(c.vsum.ensure(6 * sizeof(u64)));
-	u64 *vs = (u64 *)c.vsum.p;
-	HIP_TRY(hipMemsetAsync(vs, 0, 6 * sizeof(u64), c.stream));
-	hipLaunchKernelGGL((rsx_checksum_pairs_kernel<KT, VT>), dim3(2048), dim3(256), 0, c.stream, (const KT *)k0, (const VT *)v0, (u64)n, ka, vs);
-	HIP_TRY(hipGetLastError());
-	rsx_info local;
-	memset(&local, 0, sizeof(local));
-	rsx_info *inf = info ? info : &local;
-	RSX_TRY((sort_pairs_device_impl<KT, VT>(c, k0, k1, v0, v1, n, dtype, order, inf)));
-	const KT *kr = inf->result_in_aux ? k1 : k0;
-	const VT *vr = inf->result_in_aux ? v1 : v0;
-	hipLaunchKernelGGL((rsx_checksum_pairs_kernel<KT, VT>), dim3(2048), dim3(256), 0, c.stream, kr, vr, (u64)n, ka, vs + 3);
-	HIP_TRY(hipGetLastError());
-	u64 h[6];
-	HIP_TRY(hipMemcpyAsync(h, vs, sizeof h, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	if (env().verify_inject)
-		h[5] ^= 1;
-	if (h[3] != 0 || h[1] != h[4] || h[2] != h[5])
-		return fail(RSX_EVERIFY, "RSX_VERIFY=2: the result of a key + payload sort of %zu pairs (route %u) is %s: %llu descents, key sum %s, pair mix %s",
-		            n, inf->hybrid, h[3] ? "not sorted" : "not a permutation of the input's pairs", (unsigned long long)h[3],
-		            h[1] == h[4] ? "kept" : "changed", h[2] == h[5] ? "kept" : "changed");
-	return RSX_OK;
-}
-
-template <typename KT, typename VT>
-int sort_pairs_device_impl(Ctx &c, KT *k0, KT *k1, VT *v0, VT *v1, size_t n, int dtype, int order, rsx_info *info)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (c.fast && n * 2 * (sizeof(KT) + sizeof(VT)) <= SMALL_PAIR_BYTES && !env().no_small_sort && !capture_armed()) {
-		ProfScope prof(1, (u64)n * 2 * (sizeof(KT) + sizeof(VT)), c.stream);
-		hipLaunchKernelGGL((rsx_small_pairs_kernel<KT, VT, false>), dim3(1), dim3(1024), 0, c.stream, (const KT *)k0, k1, v0, v1,
-		                   (u32)n, ka, c.dev_host_plan);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const Plan p = *c.host_plan;
-		info_from_plan(info, p);
-		if (info) {
-			info->early_exit = p.sorted ? 2 : 0;
-			info->result_in_aux = p.ncols & 1;
-		}
-		return RSX_OK;
-	}
-	if constexpr (sizeof(KT) == 4 && sizeof(VT) == 4) {
-		if (blind_wanted<KT>(c, n, sizeof(VT))) {
-			// all sizeof(KT) columns kept (pairs_blind: the sample proves it): the result lies where an even number of passes ends
-			int done = 0;
-			RSX_TRY((pairs_blind<KT, VT>(c, k0, v0, k0, v0, n, ka, info, &done, k1, v1)));
-			if (done) {
-				if (info)
-					info->result_in_aux = 0;
-				return RSX_OK;
-			}
-		}
-	}
-	Plan plan;
-	RSX_TRY(plan_phase<KT>(c, k0, n, ka, &plan, 0, (c.fast && !capture_armed() && !verify_mode()) ? hybrid_caps_pairs<KT>(n, sizeof(VT), true) : HybCaps{0, 0, 0, 0}));
-	info_from_plan(info, plan);
-	RSX_TRY(capture_hist(c, n, sizeof(KT)));
-	if (plan.sorted)
-		return finish_sorted(info);
-	if constexpr (sizeof(KT) == 4 && sizeof(VT) == 4) {
-		if (plan.hyb == HYB_ONE_LEVEL) {
-			// one MSB pass and the pairs' leaves (mid-size arrays)
-			const u32 top = plan.cols[plan.ncols - 1];
-			RSX_TRY((scatter_pass<KT, VT>(c, k0, k1, v0, v1, n, 8 * top, c.ghist() + 256 * top, ka, 0u)));
-			const bool in_aux = (plan.ncols & 1) != 0;
-			RSX_TRY((pairs_one_level<KT, VT>(c, k1, v1, in_aux ? k1 : k0, in_aux ? v1 : v0, n, ka)));
-			if (info) {
-				info->result_in_aux = in_aux;
-				info->hybrid = 1;
-			}
-			return RSX_OK;
-		}
-		if (plan.hyb == HYB_TWO_LEVEL) {
-			// two MSB passes (the second into slots) and leaves; on a slot's overflow: one pass per column, from (k0, v0) again
-			// (RSX_NO_SLACK=1: the second pass counted first and written to (k0, v0), which pass 1 has read; a bucket too large
-			// for the leaves is known before that pass)
-			const u32 top = plan.cols[plan.ncols - 1];
-			RSX_TRY((scatter_pass<KT, VT>(c, k0, k1, v0, v1, n, 8 * top, c.ghist() + 256 * top, ka, 0u)));
-			const bool in_aux = (plan.ncols & 1) != 0;
-			bool ok = false;
-			RSX_TRY((pairs_two_level<KT, VT>(c, k1, v1, in_aux ? k1 : k0, in_aux ? v1 : v0, n, ka, &ok, k0, v0)));
-			if (ok) {
-				if (info) {
-					info->result_in_aux = in_aux;
-					info->hybrid = env().no_slack ? 2 : 4;
-				}
-				return RSX_OK;
-			}
-		}
-	}
-	KT *kc = k0, *ko = k1;
-	VT *vc = v0, *vo = v1;
-	for (u32 i = 0; i < plan.ncols; ++i) {
-		const u32 col = plan.cols[i];
-		RSX_TRY((scatter_pass<KT, VT>(c, kc, ko, vc, vo, n, 8 * col, c.ghist() + 256 * col, ka, hot_flags(plan.hot, col))));
-		std::swap(kc, ko);
-		std::swap(vc, vo);
-	}
-	if (info)
-		info->result_in_aux = kc == k1;
-	return RSX_OK;
-}
-
-// ---- rank (stable argsort) ----------------------------------------------------------
-// index halves H0 = ib, H1 = ib + n ping-pong exactly as radix_sort_rank.hpp:77-89;
-// the keys travel with the indices through two workspace
-// buffers instead of being gathered through the index as Listing 6 does.
-// (a key type no wider than KT: keeps the instantiations of impossible combinations out of the build)
-template <typename KT, typename N> using NarrowerOr = typename std::conditional<(sizeof(N) < sizeof(KT)), N, KT>::type;
-
-// one pass of a rank sort over keys currently held as KCUR (the raw KT keys until the first narrowing, KDF-applied after)
-template <typename KCUR, typename KT, typename IT>
-int rank_pass(Ctx &c, const void *kin, void *kout, u32 out_bytes, const IT *vin, IT *vout, size_t n, u32 shift, const u64 *gbase,
-              const KdfArgs<KT> &ka0, bool applied, u32 flags, u32 oshift)
-{
-	KdfArgs<KCUR> ka{0, 0, 0};
-	if constexpr (std::is_same<KCUR, KT>::value)
-		if (!applied)
-			ka = ka0;
-	return scatter_pass_to<KCUR, IT>(c, (const KCUR *)kin, kout, out_bytes, vin, vout, n, shift, gbase, ka, flags, oshift);
-}
-
-// want_half: -1 = the half the number of kept columns dictates (radix_sort_rank.hpp:91); 0 / 1 = leave the ranks in that half
-// whatever the number of passes is (the first pass generates its indices, so it can write to either half).
-template <typename KT, typename IT>
-int sort_rank_device_impl(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, int order, void **result, rsx_info *info, int want_half);
-
-// RSX_VERIFY=2: the ranks must be a permutation of 0 .. n-1 (sum and mix) through which the keys do not descend, equal keys in
-// index order (radix_sort_rank.hpp:82-90: stable) -- checked on the device, whatever route the sort took.
-template <typename KT, typename IT>
-int sort_rank_device(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, int order, void **result, rsx_info *info, int want_half = -1)
-{
-	RSX_TRY((sort_rank_device_impl<KT, IT>(c, src, ib, n, dtype, order, result, info, want_half)));
-	if (!env().verify_whole || n < 2)
-		return RSX_OK;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	RSX_TRY(c.vsum.ensure(6 * sizeof(u64)));
-	u64 *vs = (u64 *)c.vsum.p;
-	HIP_TRY(hipMemsetAsync(vs, 0, 6 * sizeof(u64), c.stream));
-	hipLaunchKernelGGL((rsx_check_ranks_kernel<KT, IT>), dim3(2048), dim3(256), 0, c.stream, (const KT *)nullptr, (const IT *)nullptr, (u64)n, ka, vs);
-	hipLaunchKernelGGL((rsx_check_ranks_kernel<KT, IT>), dim3(2048), dim3(256), 0, c.stream, src, (const IT *)*result, (u64)n, ka, vs + 3);
-	HIP_TRY(hipGetLastError());
-	u64 h[6];
-	HIP_TRY(hipMemcpyAsync(h, vs, sizeof h, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
-	if (env().verify_inject)
-		h[5] ^= 1;
-	if (h[3] != 0 || h[1] != h[4] || h[2] != h[5])
-		return fail(RSX_EVERIFY, "RSX_VERIFY=2: the ranks of a sort of %zu keys (route %u) are %s: %llu places out of order, rank sum %s, rank mix %s",
-		            n, info ? info->hybrid : 0u, h[3] ? "not the stable order" : "not a permutation of 0 .. n-1", (unsigned long long)h[3],
-		            h[1] == h[4] ? "right" : "wrong", h[2] == h[5] ? "right" : "wrong");
-	return RSX_OK;
-}
-
-template <typename KT, typename IT>
-int sort_rank_device_impl(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, int order, void **result, rsx_info *info, int want_half)
-{
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (c.fast && n * 2 * (sizeof(KT) + sizeof(IT)) <= SMALL_PAIR_BYTES && !env().no_small_sort && !capture_armed() &&
-	    want_half < 0) {
-		ProfScope prof(1, (u64)n * (sizeof(KT) + 2 * sizeof(IT)), c.stream);
-		hipLaunchKernelGGL((rsx_small_pairs_kernel<KT, IT, true>), dim3(1), dim3(1024), 0, c.stream, src, (KT *)nullptr, ib, ib + n,
-		                   (u32)n, ka, c.dev_host_plan);
-		HIP_TRY(hipGetLastError());
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		const Plan p = *c.host_plan;
-		info_from_plan(info, p);
-		if (info) {
-			info->early_exit = p.sorted ? 2 : 0;
-			info->result_in_aux = p.ncols & 1;
-		}
-		*result = (p.ncols & 1) ? ib + n : ib;   // radix_sort_rank.hpp:91 (sorted: first half = iota)
-		return RSX_OK;
-	}
-	if constexpr (sizeof(KT) == 4 && sizeof(IT) == 4) {
-		if (want_half < 0 && !env().compact_bits && blind_wanted<KT>(c, n, sizeof(IT), true)) {
-			int done = 0;
-			// (spare buffers: the index buffer's two halves -- the second one, which the reference's passes ping-pong through
-			// (radix_sort_rank.hpp:77-91), for the keys' level-1 slots)
-			RSX_TRY((pairs_blind<KT, IT>(c, src, (const IT *)nullptr, (KT *)nullptr, ib, n, ka, info, &done, (KT *)(ib + n), ib)));
-			if (done) {   // four kept columns: the ranks are in the first half (radix_sort_rank.hpp:91)
-				*result = ib;
-				if (info)
-					info->result_in_aux = 0;
-				return RSX_OK;
-			}
-		}
-	}
-	Plan plan;
-	RSX_TRY(plan_phase<KT>(c, src, n, ka, &plan, 0,
-	                       (c.fast && want_half < 0 && !capture_armed() && !verify_mode() && !env().compact_bits)
-	                           ? hybrid_caps_pairs<KT>(n, sizeof(IT)) : HybCaps{0, 0, 0, 0}));
-	info_from_plan(info, plan);
-	RSX_TRY(capture_hist(c, n, sizeof(KT)));
-	if constexpr (sizeof(KT) == 4 && sizeof(IT) == 4) {
-		if (!plan.sorted && plan.hyb == HYB_ONE_LEVEL && want_half < 0) {
-			// mid-size arrays: one MSB pass of (key, index), which makes the indices, and the pairs' leaves write the ranks
-			const u32 P = plan.ncols, top = plan.cols[P - 1];
-			RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-			IT *fin = (P & 1) ? ib + n : ib, *scratch = (P & 1) ? ib : ib + n;
-			RSX_TRY((scatter_pass<KT, IT>(c, src, (KT *)c.keys[0].p, (const IT *)fin, scratch, n, 8 * top, c.ghist() + 256 * top, ka,
-			                              (u32)SCATTER_GEN_INDEX)));
-			RSX_TRY((pairs_one_level<KT, IT>(c, (const KT *)c.keys[0].p, (const IT *)scratch, (KT *)nullptr, fin, n, ka)));
-			*result = fin;
-			if (info) {
-				info->result_in_aux = fin != ib;
-				info->hybrid = 1;
-			}
-			return RSX_OK;
-		}
-		if (!plan.sorted && plan.hyb == HYB_TWO_LEVEL && want_half < 0) {
-			// Keys spread over their top two columns (cfg 4 (i)): two MSB passes of (key, index) -- the first makes the indices,
-			// the second goes into slots -- and leaves that write the ranks where the parity rule says (radix_sort_rank.hpp:91).
-			// On a slot's overflow nothing has been written to that half: the ordinary passes follow.
-			const u32 P = plan.ncols, top = plan.cols[P - 1];
-			RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-			IT *fin = (P & 1) ? ib + n : ib, *scratch = (P & 1) ? ib : ib + n;
-			RSX_TRY((scatter_pass<KT, IT>(c, src, (KT *)c.keys[0].p, (const IT *)fin, scratch, n, 8 * top, c.ghist() + 256 * top, ka,
-			                              (u32)SCATTER_GEN_INDEX)));
-			bool ok = false;
-			RSX_TRY((pairs_two_level<KT, IT>(c, (const KT *)c.keys[0].p, (const IT *)scratch, (KT *)nullptr, fin, n, ka, &ok)));
-			if (ok) {
-				*result = fin;
-				if (info) {
-					info->result_in_aux = fin != ib;
-					info->hybrid = 4;
-				}
-				return RSX_OK;
-			}
-		}
-	}
-	if (plan.sorted) {                       // radix_sort_rank.hpp:52,:55-57: first half = iota
-		hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, ib, (u64)n);
-		HIP_TRY(hipGetLastError());
-		return finish_sorted(info, result, ib);
-	}
-	const u32 P = plan.ncols;
-	// README.md:716-758, "key compaction" (SURVEY.md 8 f4), behind RSX_COMPACT_BITS=1: when the bits that vary among the
-	// keys (plan.vary, read off the histograms) fit fewer bytes than there are varying byte columns, the keys' varying bits
-	// are packed together (one elementwise pass) and the packed values are rank-sorted instead: ceil(bits / 8) passes over
-	// narrower keys.  The ranks are the same (all other bits are equal in every key) and they are left in the half the
-	// reference's number of passes dictates.
-	if (want_half < 0 && c.fast && sizeof(IT) == 4 && P > 1) {
-		const bool compact_on = env().compact_bits;
-		const u64 vary = ((u64)plan.vary_hi << 32) | plan.vary_lo;
-		const u32 bits = (u32)__builtin_popcountll(vary), P2 = (bits + 7) / 8;
-		BitRuns runs;
-		if (compact_on && vary && P2 < P && bit_runs(vary, &runs)) {
-			const u32 ob = P2 <= 1 ? 1 : P2 <= 2 ? 2 : P2 <= 4 ? 4 : 8;
-			RSX_TRY(c.ckeys.ensure(n * ob));
-			const dim3 grid(4096), block(256);
-			rsx_info inner;
-			int rc = RSX_EINVAL;
-			const int half = (int)(P & 1);
-			if (ob == 1) {
-				hipLaunchKernelGGL((rsx_compact_bits_kernel<KT, uint8_t>), grid, block, 0, c.stream, src, (uint8_t *)c.ckeys.p, (u64)n, ka, runs);
-				rc = sort_rank_device<uint8_t, IT>(c, (const uint8_t *)c.ckeys.p, ib, n, RSX_U8, RSX_ASCENDING, result, &inner, half);
-			} else if (ob == 2) {
-				hipLaunchKernelGGL((rsx_compact_bits_kernel<KT, uint16_t>), grid, block, 0, c.stream, src, (uint16_t *)c.ckeys.p, (u64)n, ka, runs);
-				rc = sort_rank_device<uint16_t, IT>(c, (const uint16_t *)c.ckeys.p, ib, n, RSX_U16, RSX_ASCENDING, result, &inner, half);
-			} else if (ob == 4) {
-				hipLaunchKernelGGL((rsx_compact_bits_kernel<KT, u32>), grid, block, 0, c.stream, src, (u32 *)c.ckeys.p, (u64)n, ka, runs);
-				rc = sort_rank_device<u32, IT>(c, (const u32 *)c.ckeys.p, ib, n, RSX_U32, RSX_ASCENDING, result, &inner, half);
-			} else {
-				hipLaunchKernelGGL((rsx_compact_bits_kernel<KT, u64>), grid, block, 0, c.stream, src, (u64 *)c.ckeys.p, (u64)n, ka, runs);
-				rc = sort_rank_device<u64, IT>(c, (const u64 *)c.ckeys.p, ib, n, RSX_U64, RSX_ASCENDING, result, &inner, half);
-			}
-			RSX_TRY(rc);
-			if (info)
-				info->result_in_aux = P & 1;   // (ncols / cols stay the reference's: those of the original keys)
-			return RSX_OK;
-		}
-	}
-	if (P > 1) {
-		RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-		if (P > 2)
-			RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
-	}
-	// want_half: the halves swap roles when the number of passes would leave the ranks in the other one
-	const bool swap_halves = want_half >= 0 && (int)(P & 1) != want_half;
-	IT *H[2] = {swap_halves ? ib + n : ib, swap_halves ? ib : ib + n};
-	if (c.fast && sizeof(IT) == 4 && !env().no_narrow_keys) {
-		// The ranks are the only output, so a pass hands on just the key bytes that later passes look at: once those fit a
-		// narrower type the keys are written as kdf(key) >> (8 * next column) in that type, and the passes after it read
-		// it with the identity KDF.  `base_col`: the column that sits in the low byte of the current representation.
-		const void *kin = src;
-		u32 in_bytes = sizeof(KT), base_col = 0;
-		bool applied = false;
-		for (u32 i = 0; i < P; ++i) {
-			const u32 col = plan.cols[i];
-			u32 flags = hot_flags(plan.hot, col);
-			if (i == 0)
-				flags |= SCATTER_GEN_INDEX;
-			if (i == P - 1)
-				flags |= SCATTER_SKIP_KEYS;
-			u32 out_bytes = in_bytes, oshift = 0, next = base_col;
-			if (i + 1 < P) {
-				const u32 need = (u32)sizeof(KT) - plan.cols[i + 1];   // bytes from the next kept column up
-				const u32 fit = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 8;
-				if (fit < in_bytes) {
-					out_bytes = fit;
-					next = plan.cols[i + 1];
-					oshift = 8 * (next - base_col);
-				}
-			}
-			void *kout = c.keys[i & 1].p;
-			const u32 shift = 8 * (col - base_col);
-			const u64 *gb = c.ghist() + 256 * col;
-			int rc = RSX_EINVAL;
-			if (in_bytes == sizeof(KT))
-				rc = rank_pass<KT, KT, IT>(c, kin, kout, out_bytes, H[i & 1], H[(i + 1) & 1], n, shift, gb, ka, applied, flags, oshift);
-			else if (in_bytes == 4)
-				rc = rank_pass<NarrowerOr<KT, u32>, KT, IT>(c, kin, kout, out_bytes, H[i & 1], H[(i + 1) & 1], n, shift, gb, ka, true,
-				                                           flags, oshift);
-			else if (in_bytes == 2)
-				rc = rank_pass<NarrowerOr<KT, uint16_t>, KT, IT>(c, kin, kout, out_bytes, H[i & 1], H[(i + 1) & 1], n, shift, gb, ka,
-				                                                true, flags, oshift);
-			else if (in_bytes == 1)
-				rc = rank_pass<uint8_t, KT, IT>(c, kin, kout, out_bytes, H[i & 1], H[(i + 1) & 1], n, shift, gb, ka, true, flags,
-				                                oshift);
-			RSX_TRY(rc);
-			if (out_bytes != in_bytes) {
-				in_bytes = out_bytes;
-				base_col = next;
-				applied = true;
-			}
-			kin = kout;
-		}
-	} else
-	for (u32 i = 0; i < P; ++i) {
-		const u32 col = plan.cols[i];
-		const KT *kin = i == 0 ? src : (const KT *)c.keys[(i - 1) & 1].p;
-		KT *kout = (KT *)c.keys[i & 1].p;
-		u32 flags = hot_flags(plan.hot, col);
-		if (i == 0)
-			flags |= SCATTER_GEN_INDEX;
-		if (i == P - 1)
-			flags |= SCATTER_SKIP_KEYS;
-		RSX_TRY((scatter_pass<KT, IT>(c, kin, kout, H[i & 1], H[(i + 1) & 1], n, 8 * col, c.ghist() + 256 * col, ka, flags)));
-	}
-	*result = H[P & 1];                      // radix_sort_rank.hpp:91
-	if (info)
-		info->result_in_aux = *result != (void *)ib;
-	return RSX_OK;
-}
-
-// ---- stable argsort, no host synchronisation: every pass is device-scheduled, the ranks always end in the FIRST half -----------
-// radix_sort_rank.hpp:97-112 for callers that cannot wait (graphs, the multi-GPU chunk pipeline).  The number of passes is only
-// known on the device, so the passes take their buffers from the plan (SCATTER_RANK_ASYNC): the last one writes the first
-// half.  Keys travel at full width (which narrower type a pass could write is a choice of kernel, i.e. the host's).
-template <typename KT, typename IT>
-int sort_rank_inplace_async(Ctx &c, const KT *src, IT *ib, size_t n, int dtype, int order)
-{
-	if (!c.fast)
-		return fail(RSX_EHIP, "rsx_sort_rank_inplace_async needs the fast scatter kernel (the device self-check failed on this device)");
-	c.async_tried_blind = false;   // (rsx_async_route reports THIS call: set again below if an attempt is enqueued)
-	c.async_small = false;
-	const KdfArgs<KT> ka = make_kdf<KT>(dtype, order);
-	if (n * 2 * (sizeof(KT) + sizeof(IT)) <= SMALL_PAIR_BYTES) {
-		hipLaunchKernelGGL((rsx_small_pairs_kernel<KT, IT, true>), dim3(1), dim3(1024), 0, c.stream, src, (KT *)nullptr, ib, ib + n,
-		                   (u32)n, ka, c.dev_host_plan, true);
-		HIP_TRY(hipGetLastError());
-		c.async_small = true;
-		return RSX_OK;
-	}
-	RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-	RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
-	const size_t status_total = status_bytes<KT, IT>(n) * sizeof(KT);
-	// the attempt without a histogram first (4-byte keys, 4-byte indices, 16 Mi .. 2^28 keys: its leaves write the ranks to the
-	// first half), the histogram-first kernels behind it gated on its verdict -- as sort_keys_inplace_async
-	int blind = 0;
-	ProfAsyncVerdict pverdict(c.stream);
-	if constexpr (sizeof(KT) == 4 && sizeof(IT) == 4) {
-		if (async_pairs_blind_ok<KT>(c, n, sizeof(IT)))
-			RSX_TRY((pairs_blind_enqueue<KT, IT>(c, src, (const IT *)nullptr, (KT *)nullptr, ib, n, ka, &blind, (KT *)(ib + n), ib)));
-	}
-	if (blind)
-		pverdict.attempt_enqueued(SegView(c).ctl());
-	c.pass_gate = blind ? SegView(c).ctl() : nullptr;
-	c.async_tried_blind = blind != 0;
-	int rc = plan_phase<KT>(c, src, n, ka, nullptr, status_total);
-	c.pass_alt = c.keys[1].p;
-	for (u32 i = 0; i < sizeof(KT) && rc == RSX_OK; ++i)   // pass i = the i-th kept column, if there is one
-		rc = scatter_pass<KT, IT>(c, src, (KT *)c.keys[0].p, ib, ib + n, n, 0, c.ghist(), ka, SCATTER_RANK_ASYNC, c.plan(), (int)i, i);
-	c.pass_alt = nullptr;
-	c.pass_gate = nullptr;
-	RSX_TRY(rc);
-	pverdict.gated_enqueued();
-	// sorted keys: no pass ran, the ranks are 0 .. n-1 (radix_sort_rank.hpp:52,:55-57)
-	hipLaunchKernelGGL((rsx_iota_if_sorted_kernel<IT>), dim3(1024), dim3(256), 0, c.stream, ib, (u64)n, (const Plan *)c.plan());
-	HIP_TRY(hipGetLastError());
-	return RSX_OK;
-}
+namespace {
 
 bool is_device_ptr(const void *p)
 {
@@ -1314,7 +441,6 @@ bool is_device_ptr(const void *p)
 	return attr.type == hipMemoryTypeDevice || attr.type == hipMemoryTypeManaged;
 }
 
-// dispatch on key width
 // ---- one plain scatter pass by the top KDF byte (rsx_msd_split_device) ---------------------------------------------
 template <typename KT>
 int msd_split(Ctx &c, const KT *src, KT *dst, size_t n, int dtype, int order, u32 col, uint64_t *top_hist)
@@ -1378,20 +504,6 @@ const char *rsx_last_error(void) { return g_err; }
 const char *rsx_version(void) { return "rsx 0.1 (gfx950)"; }
 size_t rsx_dtype_size(rsx_dtype dtype) { return dtype_size(dtype); }
 
-size_t rsx_workspace_bytes(size_t n, rsx_dtype dtype, size_t payload_bytes)
-{
-	const size_t kb = dtype_size(dtype);
-	if (!kb)
-		return 0;
-	// upper bound over the kernels' shapes: quarter tiles (8 Ki elements, 4 Ki with an 8-byte element), a region of status
-	// words per pass, the histogram kernel's rows (at most 512 workgroups)
-	const size_t elem = kb > payload_bytes ? kb : payload_bytes;
-	const size_t tile = elem == 8 ? 4096 : 8192;
-	const size_t tiles = (n + tile - 1) / tile;
-	const size_t status = (256 + tiles * 256 * (n >= (1ull << 30) ? 8 : 4)) * kb;
-	return 512 + kb * 256 * 8 + ((status + 255) & ~(size_t)255) + (size_t)512 * kb * 256 * 4 + 256;
-}
-
 void rsx_release(void)
 {
 	std::lock_guard<std::mutex> lock(g_mu);
@@ -1417,170 +529,10 @@ void rsx_release(void)
 	g_multi_bufs.clear();
 }
 
-namespace {
-
-// A context whose device state lies in the caller's workspace: [flags 256][plan 64 + pad][histogram][status regions]
-// [histogram rows].  Everything a captured graph of the *_ws entry points refers to is inside that workspace.
-int borrow_ctx(Ctx &v, void *stream, void *ws, size_t ws_bytes, size_t n, size_t kb, size_t status_total, char **end = nullptr)
-{
-	// (no context of the library's own is created or touched: the call may be inside a stream capture, where nothing may
-	// be allocated; the device self-check has run when any other entry point was used before, otherwise it runs now)
-	int dev = 0;
-	{
-		std::lock_guard<std::mutex> lock(g_mu);
-		if (probe_devices() <= 0)
-			return fail(RSX_ENODEVICE, "no gfx950 (MI355X) device visible to HIP; this library has no CPU path");
-		HIP_TRY(hipGetDevice(&dev));
-		hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-		if (g_lds_order_ok.find(dev) == g_lds_order_ok.end() && hipStreamIsCapturing((hipStream_t)stream, &cap) == hipSuccess &&
-		    cap != hipStreamCaptureStatusNone)
-			return fail(RSX_EINVAL, "the library's first use on this device is inside a stream capture: call rsx_device_count() "
-			                        "and any sort (or rsx_sort_inplace_async_ws itself) once before capturing -- the device "
-			                        "self-check cannot run inside a capture");
-		(void)hipGetLastError();
-		if (!lds_order_selfcheck(dev))
-			return fail(RSX_EHIP, "the device-scheduled sorts need the fast scatter kernel (the device self-check failed on this device)");
-	}
-	if (((uintptr_t)ws & 255) != 0)
-		return fail(RSX_EINVAL, "the workspace must be 256-byte aligned");
-	const size_t hist_bytes = kb * 256 * sizeof(u64), hpart_bytes = (size_t)512 * kb * 256 * sizeof(u32);
-	const size_t need = 512 + hist_bytes + ((status_total + 255) & ~(size_t)255) + hpart_bytes;
-	if (!ws || ws_bytes < need)
-		return fail(RSX_EINVAL, "workspace of %zu bytes, %zu needed for %zu keys (rsx_workspace_bytes gives an upper bound)", ws_bytes, need, n);
-	char *p = (char *)ws;
-	v.device = dev;
-	v.stream = (hipStream_t)stream;
-	v.fast = true;
-	v.small.borrow(p, 256);
-	v.dev_host_plan = (Plan *)(p + 256);          // (the kernels' second copy of the plan: nobody reads it on the host)
-	v.host_plan = nullptr;
-	p += 512;
-	v.hist.borrow(p, hist_bytes);
-	p += hist_bytes;
-	v.status.borrow(p, (status_total + 255) & ~(size_t)255);
-	p += (status_total + 255) & ~(size_t)255;
-	v.hpart.borrow(p, hpart_bytes);
-	if (end)
-		*end = p + hpart_bytes;
-	return RSX_OK;
-}
-
-}  // namespace
-
 int rsx_capture_histogram(uint64_t *hist, size_t entries)
 {
 	g_capture_dst = (u64 *)hist;
 	g_capture_entries = hist ? entries : 0;
-	return RSX_OK;
-}
-
-int rsx_sort_inplace_async(void *d_buf, void *d_scratch, size_t n, rsx_dtype dtype, rsx_order order, void *stream)
-{
-	if (!dtype_size(dtype) || (n && (!d_buf || !d_scratch)))
-		return fail(RSX_EINVAL, "rsx_sort_inplace_async: bad argument");
-	if (n < 2)
-		return RSX_OK;
-	RSX_LOCKED_CTX(c, stream);
-	AsyncScope async_scope((hipStream_t)stream);
-	AsyncSetScope set_scope(*c);
-	RSX_DISPATCH_KT(dtype, return sort_keys_inplace_async<KT>(*c, (KT *)d_buf, (KT *)d_scratch, n, dtype, order));
-	return RSX_OK;
-}
-
-int rsx_sort_inplace_async_hint(void *d_buf, void *d_scratch, size_t n, rsx_dtype dtype, rsx_order order, void *stream, uint32_t hints)
-{
-	if (!dtype_size(dtype) || (n && (!d_buf || !d_scratch)))
-		return fail(RSX_EINVAL, "rsx_sort_inplace_async_hint: bad argument");
-	if (n < 2)
-		return RSX_OK;
-	RSX_LOCKED_CTX(c, stream);
-	AsyncScope async_scope((hipStream_t)stream);
-	AsyncSetScope set_scope(*c);
-	struct HintScope {   // (the sample kernel of the attempt enqueued by this call reads them: blind_enqueue)
-		Ctx &c;
-		HintScope(Ctx &c_, u32 h) : c(c_) { c.hints = h; }
-		~HintScope() { c.hints = 0; }
-	} hint_scope(*c, (u32)hints);
-	RSX_DISPATCH_KT(dtype, return sort_keys_inplace_async<KT>(*c, (KT *)d_buf, (KT *)d_scratch, n, dtype, order));
-	return RSX_OK;
-}
-
-int rsx_sort_inplace_async_ws(void *d_buf, void *d_scratch, size_t n, rsx_dtype dtype, rsx_order order, void *d_workspace,
-                              size_t workspace_bytes, void *stream)
-{
-	const size_t kb = dtype_size(dtype);
-	if (!kb || (n && (!d_buf || !d_scratch)))
-		return fail(RSX_EINVAL, "rsx_sort_inplace_async_ws: bad argument");
-	if (n < 2)
-		return RSX_OK;
-	Ctx view;
-	size_t status_total = 0;
-	RSX_DISPATCH_KT(dtype, status_total = (status_bytes<KT, NoVal>(n) * sizeof(KT)));
-	char *end = nullptr;
-	RSX_TRY(borrow_ctx(view, stream, d_workspace, workspace_bytes, n, kb, status_total, &end));
-	// a workspace sized by rsx_workspace_bytes_fast also holds the slots of a sort without a histogram: the attempt is made in it
-	RSX_DISPATCH_KT(dtype, borrow_blind<KT>(view, end, (char *)d_workspace + workspace_bytes, n));
-	AsyncScope async_scope((hipStream_t)stream);
-	RSX_DISPATCH_KT(dtype, return sort_keys_inplace_async<KT>(view, (KT *)d_buf, (KT *)d_scratch, n, dtype, order));
-	return RSX_OK;
-}
-
-size_t rsx_workspace_bytes_fast(size_t n, rsx_dtype dtype)
-{
-	const size_t kb = dtype_size(dtype);
-	if (!kb)
-		return 0;
-	size_t g = 0, sg = 0, s1 = 0, s2 = 0;
-	if (kb >= 4 && n >= ((size_t)1 << 22) && n < ((size_t)1 << 30)) {
-		if (kb == 4)
-			blind_sizes<u32>(n, &g, &sg, &s1, &s2);
-		else
-			blind_sizes<u64>(n, &g, &sg, &s1, &s2);
-	}
-	return ((rsx_workspace_bytes(n, dtype, 0) + 255) & ~(size_t)255) + 256 + g + sg + s1 + s2;
-}
-
-int rsx_async_route_ws(const void *d_workspace, size_t workspace_bytes, size_t n, rsx_dtype dtype, void *stream, uint32_t *route)
-{
-	const size_t kb = dtype_size(dtype);
-	if (!route || !d_workspace || !kb)
-		return fail(RSX_EINVAL, "rsx_async_route_ws: bad argument");
-	*route = 0;
-	HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-	Plan plan;
-	HIP_TRY(hipMemcpy(&plan, (const char *)d_workspace + 64, sizeof(plan), hipMemcpyDeviceToHost));
-	// (the layout of borrow_ctx / borrow_blind: the control block of the attempt lies behind the histogram kernel's rows and gscan)
-	size_t status_total = 0;
-	RSX_DISPATCH_KT(dtype, status_total = (status_bytes<KT, NoVal>(n) * sizeof(KT)));
-	const size_t minimal = 512 + kb * 256 * sizeof(u64) + ((status_total + 255) & ~(size_t)255) + (size_t)512 * kb * 256 * sizeof(u32);
-	if (kb >= 4 && workspace_bytes >= rsx_workspace_bytes_fast(n, dtype) && n >= ((size_t)1 << 22) && n < ((size_t)1 << 30)) {
-		const char *p = (const char *)(((uintptr_t)d_workspace + minimal + 255) & ~(uintptr_t)255) + 256 * sizeof(u64);
-		SegCtl ctl;
-		HIP_TRY(hipMemcpy(&ctl, p, sizeof(ctl), hipMemcpyDeviceToHost));
-		if (ctl.mode == SEG_MODE_LEAVES && ctl.blind == BLIND_GO) {
-			*route = 5;
-			return RSX_OK;
-		}
-	}
-	if (!plan.sorted && plan.hyb == HYB_ONE_LEVEL)
-		*route = 1;
-	return RSX_OK;
-}
-
-int rsx_sort_pairs_inplace_async_ws(void *d_keys, void *d_keys_scratch, void *d_vals, void *d_vals_scratch, size_t n, rsx_dtype dtype,
-                                    size_t payload_bytes, rsx_order order, void *d_workspace, size_t workspace_bytes, void *stream)
-{
-	const size_t kb = dtype_size(dtype);
-	if (!kb || (payload_bytes != 4 && payload_bytes != 8) || (n && (!d_keys || !d_keys_scratch || !d_vals || !d_vals_scratch)))
-		return fail(RSX_EINVAL, "rsx_sort_pairs_inplace_async_ws: bad argument");
-	if (n < 2)
-		return RSX_OK;
-	Ctx view;
-	size_t status_total = 0;
-	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, status_total = (status_bytes<KT, VT>(n) * sizeof(KT)));
-	RSX_TRY(borrow_ctx(view, stream, d_workspace, workspace_bytes, n, kb, status_total));
-	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_inplace_async<KT, VT>(view, (KT *)d_keys, (KT *)d_keys_scratch, (VT *)d_vals,
-	                                                                                     (VT *)d_vals_scratch, n, dtype, order)));
 	return RSX_OK;
 }
 
@@ -1611,305 +563,9 @@ void rsx_release_stream(void *stream)
 	delete c;
 }
 
-int rsx_sort_pairs_inplace_async(void *d_keys, void *d_keys_scratch, void *d_vals, void *d_vals_scratch, size_t n, rsx_dtype dtype,
-                                 size_t payload_bytes, rsx_order order, void *stream)
-{
-	if (!dtype_size(dtype) || (payload_bytes != 4 && payload_bytes != 8) ||
-	    (n && (!d_keys || !d_keys_scratch || !d_vals || !d_vals_scratch)))
-		return fail(RSX_EINVAL, "rsx_sort_pairs_inplace_async: bad argument");
-	if (n < 2)
-		return RSX_OK;
-	RSX_LOCKED_CTX(c, stream);
-	AsyncScope async_scope((hipStream_t)stream);
-	AsyncSetScope set_scope(*c);
-	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_inplace_async<KT, VT>(*c, (KT *)d_keys, (KT *)d_keys_scratch, (VT *)d_vals,
-	                                                                                     (VT *)d_vals_scratch, n, dtype, order)));
-	return RSX_OK;
-}
-
-int rsx_sort_device(void *d_src, void *d_aux, size_t n, rsx_dtype dtype, rsx_order order, void *stream, void **result,
-                    rsx_info *info)
-{
-	info_clear(info, dtype);
-	if (!dtype_size(dtype) || !result || (n && (!d_src || !d_aux)))
-		return fail(RSX_EINVAL, "rsx_sort_device: bad argument");
-	if (n < 2) {                             // radix_sort.hpp:100-101
-		*result = d_src;
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_LOCKED_CTX(c, stream);
-	RSX_DISPATCH_KT(dtype, return sort_keys_device<KT>(*c, (KT *)d_src, (KT *)d_aux, n, dtype, order, result, info));
-	return RSX_OK;
-}
-
-int rsx_sort_pairs_device(void *d_keys, void *d_keys_aux, void *d_vals, void *d_vals_aux, size_t n, rsx_dtype dtype,
-                          size_t payload_bytes, rsx_order order, void *stream, rsx_info *info)
-{
-	info_clear(info, dtype);
-	if (!dtype_size(dtype) || (payload_bytes != 4 && payload_bytes != 8) ||
-	    (n && (!d_keys || !d_keys_aux || !d_vals || !d_vals_aux)))
-		return fail(RSX_EINVAL, "rsx_sort_pairs_device: bad argument");
-	if (n < 2) {
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_LOCKED_CTX(c, stream);
-	RSX_DISPATCH_KT_W(dtype, payload_bytes, VT, return (sort_pairs_device<KT, VT>(*c, (KT *)d_keys, (KT *)d_keys_aux, (VT *)d_vals,
-	                                                                              (VT *)d_vals_aux, n, dtype, order, info)));
-	return RSX_OK;
-}
-
-int rsx_sort_rank_inplace_async(const void *d_src, void *d_index_buffer, size_t n, rsx_dtype dtype, size_t idx_bytes,
-                                rsx_order order, void *stream)
-{
-	if (!dtype_size(dtype) || (idx_bytes != 4 && idx_bytes != 8) || (n && (!d_src || !d_index_buffer)))
-		return fail(RSX_EINVAL, "rsx_sort_rank_inplace_async: bad argument");
-	if (idx_bytes == 4 && n > (1ull << 32))
-		return fail(RSX_EINVAL, "rsx_sort_rank_inplace_async: n does not fit a 4-byte index");
-	if (n == 0)
-		return RSX_OK;                       // radix_sort_rank.hpp:28-32
-	RSX_LOCKED_CTX(c, stream);
-	AsyncScope async_scope((hipStream_t)stream);
-	AsyncSetScope set_scope(*c);
-	if (n == 1) {
-		HIP_TRY(hipMemsetAsync(d_index_buffer, 0, idx_bytes, c->stream));
-		return RSX_OK;
-	}
-	RSX_DISPATCH_KT_W(dtype, idx_bytes, IT, return (sort_rank_inplace_async<KT, IT>(*c, (const KT *)d_src, (IT *)d_index_buffer, n, dtype, order)));
-	return RSX_OK;
-}
-
-int rsx_verify_poll(void *stream, uint64_t *mismatches)
-{
-	if (mismatches)
-		*mismatches = 0;
-	RSX_LOCKED_CTX(c, stream);
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (!c->vasync.p)
-		return RSX_OK;
-	u64 bad = 0;
-	HIP_TRY(hipMemcpy(&bad, c->vasync.p, sizeof(bad), hipMemcpyDeviceToHost));
-	if (mismatches)
-		*mismatches = bad;
-	if (bad) {
-		HIP_TRY(hipMemset(c->vasync.p, 0, 8));
-		return fail(RSX_EVERIFY, "RSX_VERIFY: a device-scheduled sort on this stream had a pass whose checked tile differs from its "
-		                         "ballot-ranked re-computation in %llu places", (unsigned long long)bad);
-	}
-	return RSX_OK;
-}
-
-int rsx_async_route(void *stream, uint32_t *route)
-{
-	if (!route)
-		return fail(RSX_EINVAL, "rsx_async_route: bad argument");
-	*route = 0;
-	RSX_LOCKED_CTX(c, stream);
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	if (c->async_small)
-		return RSX_OK;   // (the one-launch sort writes no device-side plan: what lies there is an earlier sort's)
-	Plan plan;
-	HIP_TRY(hipMemcpy(&plan, c->async_plan(), sizeof(plan), hipMemcpyDeviceToHost));
-	if (c->async_tried_blind && c->seg.p) {
-		SegCtl ctl;
-		HIP_TRY(hipMemcpy(&ctl, c->seg.p, sizeof(ctl), hipMemcpyDeviceToHost));
-		if (getenv("RSX_DEBUG_ROUTE"))   // (what the device left behind: which test ended an attempt)
-			fprintf(stderr, "rsx_async_route: blind %u mode %u overflow %u ntiles %u nleaf %u maxleaf %u shift1 %u shift2 %u cmask %08x%08x "
-			                "narrow %u compact %u leaf16 %u boff_skip %u boff_next %u slots in the second buffer %u cap1 %u cap2 %u\n",
-			        ctl.blind, ctl.mode, ctl.overflow, ctl.ntiles, ctl.nleaf, ctl.maxleaf, ctl.shift1, ctl.shift2, ctl.cmask_hi, ctl.cmask_lo,
-			        ctl.narrow, ctl.compact, ctl.leaf16, ctl.boff_skip, ctl.boff_next, c->slack1_lo, c->slack1_cap, c->slack_cap);
-		if (ctl.mode == SEG_MODE_LEAVES) {
-			*route = 5;
-			return RSX_OK;
-		}
-	}
-	if (!plan.sorted && plan.hyb == HYB_ONE_LEVEL)
-		*route = 1;
-	return RSX_OK;
-}
-
-int rsx_sort_rank_device(const void *d_src, void *d_index_buffer, size_t n, rsx_dtype dtype, size_t idx_bytes,
-                         rsx_order order, void *stream, void **result, rsx_info *info)
-{
-	info_clear(info, dtype);
-	if (!dtype_size(dtype) || (idx_bytes != 4 && idx_bytes != 8) || !result || (n && (!d_src || !d_index_buffer)))
-		return fail(RSX_EINVAL, "rsx_sort_rank_device: bad argument");
-	if (idx_bytes == 4 && n > (1ull << 32))
-		return fail(RSX_EINVAL, "rsx_sort_rank_device: n does not fit a 4-byte index");
-	*result = d_index_buffer;
-	if (n == 0) {                            // radix_sort_rank.hpp:28-32
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_LOCKED_CTX(c, stream);
-	if (n == 1) {
-		HIP_TRY(hipMemsetAsync(d_index_buffer, 0, idx_bytes, c->stream));
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_DISPATCH_KT_W(dtype, idx_bytes, IT, return (sort_rank_device<KT, IT>(*c, (const KT *)d_src, (IT *)d_index_buffer, n, dtype, order,
-	                                                                         result, info)));
-	return RSX_OK;
-}
-
-// host arrays the one-launch kernels take (sort_keys_device, sort_rank_device: the same conditions)
-static bool host_small_path(const Ctx &c, size_t key_bytes)
-{
-	return c.fast && key_bytes <= SMALL_SORT_BYTES && !env().no_small_sort && !env().no_host_small && !capture_armed();
-}
-
-int rsx_sort(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order order, void **result, rsx_info *info)
-{
-	info_clear(info, dtype);
-	const size_t kb = dtype_size(dtype);
-	if (!kb || !result || (n && (!src || !aux)))
-		return fail(RSX_EINVAL, "rsx_sort: bad argument");
-	if (n < 2) {                             // radix_sort.hpp:100-101
-		*result = src;
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_LOCKED_CTX(c, nullptr);
-	if (is_device_ptr(src)) {
-		if (!is_device_ptr(aux))
-			return fail(RSX_EINVAL, "rsx_sort: src is a device pointer but aux is not");
-		RSX_TRY(rsx_sort_device(src, aux, n, dtype, order, nullptr, result, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	if (host_small_path(*c, n * kb)) {
-		// small host arrays: the one-launch kernel reads the keys from pinned memory and writes the result there
-		RSX_TRY(c->ensure_hstage());
-		memcpy(c->hstage, src, n * kb);
-		void *dres = nullptr;
-		rsx_info li;
-		RSX_TRY(rsx_sort_device(c->hstage_dev, c->hstage_dev + SMALL_SORT_BYTES, n, dtype, order, nullptr, &dres, &li));
-		if (info)
-			*info = li;
-		if (li.early_exit) {
-			*result = src;
-			return RSX_OK;
-		}
-		void *hres = li.result_in_aux ? aux : src;
-		memcpy(hres, c->hstage + ((char *)dres - c->hstage_dev), n * kb);
-		*result = hres;
-		return RSX_OK;
-	}
-	// host buffers: stage over PCIe, sort in HBM, bring the result back into the
-	// buffer the returned-pointer rule names (the other one is left as it was)
-	RSX_TRY(c->keys[0].ensure(n * kb));
-	RSX_TRY(c->keys[1].ensure(n * kb));
-	HostRegScope reg_src(src, n * kb), reg_aux(aux, n * kb);   // (RSX_HOST_REGISTER=1: pinned until this call returns)
-	HIP_TRY(hipMemcpyAsync(c->keys[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	void *dres = nullptr;
-	rsx_info li;
-	RSX_TRY(rsx_sort_device(c->keys[0].p, c->keys[1].p, n, dtype, order, nullptr, &dres, &li));
-	if (info)
-		*info = li;
-	if (li.early_exit) {
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		*result = src;
-		return RSX_OK;
-	}
-	void *hres = li.result_in_aux ? aux : src;
-	HIP_TRY(hipMemcpyAsync(hres, dres, n * kb, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	*result = hres;
-	return RSX_OK;
-}
-
-int rsx_sort_rank(const void *src, void *index_buffer, size_t n, rsx_dtype dtype, size_t idx_bytes, rsx_order order,
-                  void **result, rsx_info *info)
-{
-	info_clear(info, dtype);
-	const size_t kb = dtype_size(dtype);
-	if (!kb || !result || (idx_bytes != 1 && idx_bytes != 2 && idx_bytes != 4 && idx_bytes != 8) ||
-	    (n && (!src || !index_buffer)))
-		return fail(RSX_EINVAL, "rsx_sort_rank: bad argument");
-	if (idx_bytes < 8 && n > (1ull << (8 * idx_bytes)))
-		return fail(RSX_EINVAL, "rsx_sort_rank: n = %zu does not fit a %zu-byte index", n, idx_bytes);
-	*result = index_buffer;
-	if (n == 0) {
-		if (info)
-			info->early_exit = 1;
-		return RSX_OK;
-	}
-	RSX_LOCKED_CTX(c, nullptr);
-	const bool dev = is_device_ptr(src);
-	if (dev != is_device_ptr(index_buffer))
-		return fail(RSX_EINVAL, "rsx_sort_rank: src and index_buffer must both be host or both be device pointers");
-	if (dev && idx_bytes >= 4) {
-		RSX_TRY(rsx_sort_rank_device(src, index_buffer, n, dtype, idx_bytes, order, nullptr, result, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	const size_t wide = idx_bytes == 8 ? 8 : 4;
-	if (!dev && host_small_path(*c, 0) && n * 2 * (kb + wide) <= SMALL_PAIR_BYTES) {
-		// small host arrays: keys read from and ranks written to pinned memory by the one-launch kernel, narrowed here
-		RSX_TRY(c->ensure_hstage());
-		memcpy(c->hstage, src, n * kb);
-		char *hib = c->hstage + SMALL_SORT_BYTES, *dib = c->hstage_dev + SMALL_SORT_BYTES;
-		void *dres = nullptr;
-		rsx_info li;
-		RSX_TRY(rsx_sort_rank_device(c->hstage_dev, dib, n, dtype, wide, order, nullptr, &dres, &li));
-		if (info)
-			*info = li;
-		const bool second = dres != (void *)dib;
-		char *out = (char *)index_buffer + (second ? n * idx_bytes : 0);
-		const char *from = hib + ((char *)dres - dib);
-		if (idx_bytes >= 4) {
-			memcpy(out, from, n * idx_bytes);
-		} else if (idx_bytes == 2) {
-			for (size_t i = 0; i < n; ++i)
-				((uint16_t *)out)[i] = (uint16_t)((const u32 *)from)[i];
-		} else {
-			for (size_t i = 0; i < n; ++i)
-				((uint8_t *)out)[i] = (uint8_t)((const u32 *)from)[i];
-		}
-		*result = out;
-		return RSX_OK;
-	}
-	// staged path: keys in recs[0] (host keys) or in place (device keys); indices computed
-	// as 4- or 8-byte values in vals[0], narrowed into vals[1] when IdxType is 1 or 2 bytes
-	const void *dkeys = src;
-	if (!dev) {
-		RSX_TRY(c->recs[0].ensure(n * kb));
-		HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-		dkeys = c->recs[0].p;
-	}
-	RSX_TRY(c->vals[0].ensure(2 * n * wide));
-	void *dres = nullptr;
-	rsx_info li;
-	RSX_TRY(rsx_sort_rank_device(dkeys, c->vals[0].p, n, dtype, wide, order, nullptr, &dres, &li));
-	if (info)
-		*info = li;
-	const bool second = dres != c->vals[0].p;
-	char *out = (char *)index_buffer + (second ? n * idx_bytes : 0);
-	const void *from = dres;
-	if (idx_bytes < 4) {
-		RSX_TRY(c->vals[1].ensure(n * idx_bytes));
-		if (idx_bytes == 1)
-			hipLaunchKernelGGL((rsx_convert_kernel<uint8_t, u32>), dim3(256), dim3(256), 0, c->stream, (uint8_t *)c->vals[1].p,
-			                   (const u32 *)dres, (u64)n);
-		else
-			hipLaunchKernelGGL((rsx_convert_kernel<uint16_t, u32>), dim3(256), dim3(256), 0, c->stream,
-			                   (uint16_t *)c->vals[1].p, (const u32 *)dres, (u64)n);
-		HIP_TRY(hipGetLastError());
-		from = c->vals[1].p;
-	}
-	HIP_TRY(hipMemcpyAsync(out, from, n * idx_bytes, dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	*result = out;
-	return RSX_OK;
-}
-
 }  // extern "C"
+
+#include "rsx_plain_api.hpp"    // the plain sorts' entry points: rsx_sort*, rsx_sort_pairs*, rsx_sort_rank*, their *_inplace_async forms, the workspace
 
 // one file per feature: its host driver (anonymous namespace) and its entry points (extern "C")
 #include "rsx_keybits_api.hpp"   // what the next three share: the sample and the plan, the bitmap, the heads, the index sort
@@ -1980,9 +636,7 @@ int rsx_msd_split_async(const void *d_src, void *d_dst, size_t n, rsx_dtype dtyp
 	const u32 col = column < 0 ? (u32)kb - 1 : (u32)column;
 	if (n == 0)
 		return RSX_OK;
-	RSX_LOCKED_CTX(c, stream);
-	AsyncScope async_scope((hipStream_t)stream);
-	AsyncSetScope set_scope(*c);
+	RSX_ASYNC_CTX(c, stream);
 	HIP_TRY(hipMemsetAsync(c->small_set(), 0, 256, c->stream));
 	RSX_DISPATCH_KT(dtype, return msd_split_known<KT>(*c, (const KT *)d_src, (KT *)d_dst, n, dtype, order, col, (const u64 *)d_hist, hot));
 	return RSX_OK;

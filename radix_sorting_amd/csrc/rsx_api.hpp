@@ -29,7 +29,23 @@
 	RSX_TRY(get_ctx(stream, &c));     \
 	std::lock_guard<std::recursive_mutex> ctx_lock(c->mu)
 
+// ... of a device-scheduled entry point (enqueue only; the stream may be capturing): marked as such to the end of the scope
+// (AsyncScope), on the set of flags that is the device-scheduled sorts' own (AsyncSetScope)
+#define RSX_ASYNC_CTX(c, stream)                    \
+	RSX_LOCKED_CTX(c, stream);                      \
+	AsyncScope async_scope((hipStream_t)(stream));  \
+	AsyncSetScope set_scope(*c)
+
 namespace {
+
+// what every plain sort refuses: an unknown dtype, a second array (payloads, indices) of other than 4- or 8-byte elements,
+// a buffer that is missing where there are keys (`bufs`: all of them are there)
+int sort_args(const char *who, rsx_dtype dtype, size_t n, bool bufs, size_t second_bytes = 4)
+{
+	if (!dtype_size(dtype) || (second_bytes != 4 && second_bytes != 8) || (n && !bufs))
+		return fail(RSX_EINVAL, "%s: bad argument", who);
+	return RSX_OK;
+}
 
 // A call that waits for the device cannot be captured (a query that fails is no refusal: the call goes on)
 int refuse_capture(void *stream, const char *who, const char *why)

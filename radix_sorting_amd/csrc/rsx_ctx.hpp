@@ -1,5 +1,5 @@
 // rsx_ctx.hpp: what every host function uses -- the error convention (fail, HIP_TRY, RSX_TRY), DevBuf, the per (device, stream) context
-// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp and rsx_seg_layout.hpp, ahead of the routes.
+// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp, rsx_seg_layout.hpp and rsx_ws_layout.hpp, ahead of the routes.
 #pragma once
 
 namespace {
@@ -248,7 +248,7 @@ struct Ctx {
 	// without the host seeing it, so it must never count into a set that a blocking sort trusts to be zero.
 	u32 gen = 0;
 	static constexpr u32 ASYNC_SET = 2, SETS = 3;
-	static constexpr size_t SMALL_BYTES = 256, HIST_SET_BYTES = 8 * 256 * sizeof(u64);
+	static constexpr size_t SMALL_BYTES = WS_FLAGS_BYTES, HIST_SET_BYTES = 8 * 256 * sizeof(u64);
 	char *small_set() const { return (char *)small.p + (small.external ? 0 : gen * SMALL_BYTES); }
 	char *small_set_other() const { return (char *)small.p + (gen ^ 1u) * SMALL_BYTES; }
 	u64 *ghist() const { return (u64 *)((char *)hist.p + (hist.external ? 0 : gen * HIST_SET_BYTES)); }
@@ -257,9 +257,9 @@ struct Ctx {
 	u32 *plan_done() const { return (u32 *)(small_set() + 52); }   // blocks of rsx_plan_kernel that are through
 	u64 *verify_bad() const { return (u64 *)(small_set() + 56); }  // RSX_VERIFY: mismatches found by rsx_verify_tile_kernel
 	u32 *hotd() const { return (u32 *)(small_set() + 16); }   // [8] hot digits per column + [1] valid bits (rsx_plan_kernel)
-	Plan *plan() const { return (Plan *)(small_set() + 64); }
+	Plan *plan() const { return (Plan *)(small_set() + WS_PLAN_OFF); }   // (a caller's workspace: WsLayout::plan_off)
 	// ... of the last device-scheduled sort of this context (rsx_async_route), whatever the blocking sorts have done since
-	const Plan *async_plan() const { return (const Plan *)((char *)small.p + (small.external ? 0 : ASYNC_SET * SMALL_BYTES) + 64); }
+	const Plan *async_plan() const { return (const Plan *)((char *)small.p + (small.external ? 0 : ASYNC_SET * SMALL_BYTES) + WS_PLAN_OFF); }
 	u32 *kept() const { return (u32 *)(small_set() + 128); }
 	u32 *colmax() const { return (u32 *)(small_set() + 192); }   // [8] largest bin per column (rsx_plan_kernel, kept[16..])
 

@@ -371,38 +371,31 @@ int sort_keys_blind(Ctx &c, KT *src, KT *aux, size_t n, KdfArgs<KT> ka, KT **res
 
 // What a sort of n keys WITHOUT a histogram needs on top of seg_bytes (blind_enqueue): the level-1 slots that do not fit the
 // caller's second buffer, the level-2 slots, the control block / tables / status words of the two passes.
-template <typename KT> void blind_sizes(size_t n, size_t *gscan, size_t *seg, size_t *slack1, size_t *slack)
+template <typename KT> WsBlind blind_sizes(size_t n)
 {
 	typedef Sc2Cfg<KT, NoVal> C2;
 	const u32 cap1 = level1_slot_cap<KT>((u32)(n >> 8)), cap2 = slot_cap_for((u32)(n >> 16));
 	const u32 lo = cap1 >= (u32)C2::TILE ? (u32)std::min<size_t>(n / cap1, 255) : 0u;
 	const size_t slot2 = (sizeof(KT) == 4 && cap2 <= dense_cap_max<KT>()) ? 2 : sizeof(KT);
-	*gscan = 256 * sizeof(u64);
-	*seg = (seg_bytes<KT>(n) + 255) & ~(size_t)255;
-	*slack1 = ((((size_t)(256 - lo) * cap1 + C2::TILE) * sizeof(KT)) + 255) & ~(size_t)255;
-	*slack = ((((size_t)65536 * cap2 + C2::TILE) * slot2) + 255) & ~(size_t)255;
+	WsBlind b;
+	b.gscan = 256 * sizeof(u64);
+	b.seg = ws_align256(seg_bytes<KT>(n));
+	b.slack1 = ws_align256(((size_t)(256 - lo) * cap1 + C2::TILE) * sizeof(KT));
+	b.slack = ws_align256(((size_t)65536 * cap2 + C2::TILE) * slot2);
+	return b;
 }
 
 // ... handed to the context if the workspace has it (rsx_workspace_bytes_fast): the attempt is then made inside the workspace
-template <typename KT> void borrow_blind(Ctx &v, char *p, char *ws_end, size_t n)
+inline void borrow_blind(Ctx &v, char *ws, size_t ws_bytes, const WsLayout &l)
 {
-	if constexpr (sizeof(KT) >= 4) {
-		size_t g, sg, s1, s2;
-		blind_sizes<KT>(n, &g, &sg, &s1, &s2);
-		p = (char *)(((uintptr_t)p + 255) & ~(uintptr_t)255);
-		if (n < ((size_t)1 << 22) || n >= ((size_t)1 << 30) || p + g + sg + s1 + s2 > ws_end)
-			return;
-		v.gscan.borrow(p, g);
-		p += g;
-		v.seg.borrow(p, sg);
-		p += sg;
-		v.slack1.borrow(p, s1);
-		p += s1;
-		v.slack.borrow(p, s2);
-		v.ws_blind = true;
-	}
+	if (!l.blind_fits(ws_bytes))
+		return;
+	v.gscan.borrow(ws + l.gscan_off, l.blind.gscan);
+	v.seg.borrow(ws + l.seg_off, l.blind.seg);
+	v.slack1.borrow(ws + l.slack1_off, l.blind.slack1);
+	v.slack.borrow(ws + l.slack_off, l.blind.slack);
+	v.ws_blind = true;
 }
-
 
 // the pairs' LDS leaves over the two-byte key slots of c.slack / c.slack_v, in shape LC (redo: only the leaves of that list)
 template <typename KT, typename VT, typename LC>

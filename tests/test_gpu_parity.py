@@ -537,7 +537,7 @@ def test_two_byte_keys_as_one_sixteen_bit_digit(dt, order, monkeypatch):
 @pytest.mark.parametrize("dt", [ol.U8, ol.I16, ol.U32, ol.I32, ol.F32, ol.U64, ol.F64])
 def test_small_host_arrays_through_pinned_staging(dt, monkeypatch):
     """rsx_sort / rsx_sort_rank on host arrays the one-launch kernels take: keys read from and results written to pinned memory
-    by the kernel itself (rsx.hip, host_small_path).  Same results, returned buffer and untouched other buffer as the staged
+    by the kernel itself (rsx_plain_api.hpp, host_small_path).  Same results, returned buffer and untouched other buffer as the staged
     path (RSX_NO_HOST_SMALL=1) and as the oracle, at sizes on either side of the limits (64 KiB of keys; 128 KiB of keys and
     two index halves), both orders, every index width that holds n."""
     kb = ol.DTYPE_SIZE[dt]
