@@ -370,6 +370,23 @@ void radix_sort_nth(const T *src, size_t n, const uint64_t *ranks, size_t m, T *
 		rsx_detail::fail("radix_sort_nth", rc);
 }
 
+// Not in the reference's header (the opposite of radix_sort_nth): where the m values vals[0 .. m-1] (any order, repeats allowed,
+// need not occur in src; neither array is written) fall in the sorted order of src.  less[j] (room for m) = the elements of src
+// whose derived key is below that of vals[j] -- std::lower_bound's position in the sorted array --, equal[j] (room for m, if
+// given) = those whose derived key equals it, bin[i] (room for n, if given) = the values at or below src[i]
+// (flags = RSX_LOCATE_BINS_BELOW: strictly below).  By bit pattern through basic_kdfs::kdf; RSX_DESCENDING for the complemented
+// order.  Any of less / equal / bin may be nullptr, not all (rsx_sort_locate).
+template <typename IdxType, typename T>
+void radix_sort_locate(const T *src, size_t n, const T *vals, size_t m, IdxType *less, IdxType *equal = nullptr, IdxType *bin = nullptr,
+                       rsx_order order = RSX_ASCENDING, uint32_t flags = 0)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_locate takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_locate: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_locate(src, n, vals, m, rsx_detail::dtype_of<T>(), order, less, equal, bin, sizeof(IdxType), flags, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_locate", rc);
+}
+
 // Not in the reference's header (its text's stability argument one level up): the stable argsort of n rows by several key
 // columns, none of which is written, into idx_out (room for n).  c0 is the MOST significant column, as in ORDER BY c0, c1, ...
 // (np.lexsort takes its keys in the reverse order); rows equal in every column come in ascending index order.  Scalar column

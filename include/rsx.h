@@ -72,6 +72,13 @@
  *   the widest packed type (2, 4 or 8 bytes); rsx_sort_lex on host buffers also the staged columns and n indices.  Freed by
  *   rsx_release / rsx_release_stream, never allocated inside a stream capture (the call refuses a capturing stream); a
  *   failed allocation fails the call with RSX_ENOMEM.
+ *   rsx_sort_locate*: in the (device, stream) context: a copy of the m values and the second buffer of its sort (4- and 8-byte
+ *   keys, and the bins of the sort route); the search route's table -- up to 4096 edges, as many 8-byte cumulative counts, and
+ *   one row of 2 x 4097 eight-byte counts per workgroup (at most 256: 16 MiB) --, the table route's two sets of counts and
+ *   offsets (1.5 MiB for 2-byte keys); the sort route keeps what rsx_sort keeps for a copy of the keys (2 n keys and the sort's
+ *   workspace); rsx_sort_locate on host buffers also the staged keys, values and outputs.  Freed by rsx_release /
+ *   rsx_release_stream, never allocated inside a stream capture (the call refuses a capturing stream).  If an allocation of
+ *   the search or table route fails the call takes the sort route.
  *
  * Environment switches (read ONCE, at the library's first call; rsx_reload_env() reads them again)
  *   RSX_VERIFY=1            after every scatter pass one tile is re-ranked without LDS
@@ -138,6 +145,11 @@
  *                           (tests run both and compare; tools/topk_probe.py times both);
  *   RSX_NTH_FORCE=1         rsx_sort_nth*: the select route whenever n >= 2 and 1 <= distinct ranks <= RSX_NTH_MAX_SELECT_RANKS;
  *                           =2: always the sort route (tests run both and compare; tools/nth_probe.py times both);
+ *   RSX_LOCATE_FORCE=2      rsx_sort_locate*: always the sort route (tests run both and compare; tools/locate_probe.py times both);
+ *   RSX_LOCATE_MAX_VALUES=k rsx_sort_locate*: the search route while there are at most k distinct values, k in 1 .. 4096 (default
+ *                           RSX_LOCATE_MAX_SEARCH_VALUES; tests lower the cut-off with it);
+ *   RSX_LOCATE_COUNTER_SETS=k  (tests, probe) the search kernel keeps k sets of its LDS counters, k in 1 .. 32 (default: as many
+ *                           as fit, at most 32);
  *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
  *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
@@ -565,6 +577,65 @@ int rsx_sort_nth_device(const void *d_src, size_t n, const uint64_t *ranks, size
 int rsx_sort_nth(const void *src, size_t n, const uint64_t *ranks, size_t m,
                  rsx_dtype dtype, rsx_order order, void *out_keys, void *out_idx, size_t idx_bytes,
                  uint64_t *n_less, uint64_t *n_equal, rsx_nth_info *info);
+
+/* ---- where given values fall in the sorted order (the opposite of rsx_sort_nth: searchsorted, bucketize, digitize, the bins of
+ *      a histogram with given edges, the parts of a split by given splitters) -------------------------------------------------- */
+
+/* For m values that need not occur among the n keys: how many keys lie below each and how many equal it, and for every key how
+ * many of the values lie at or below it -- without sorting the keys where the values are few.
+ *   - Result: let K(x) be the derived key of x under dtype and order (the KDF, complemented for RSX_DESCENDING: what the sorts
+ *     order by).  For every j < m: less[j] = #{ i : K(src[i]) < K(vals[j]) } -- searchsorted(sorted src, vals[j], 'left') --
+ *     and equal[j] = #{ i : K(src[i]) == K(vals[j]) }; less + equal is searchsorted's 'right'.  For every i < n:
+ *     bin[i] = #{ j : K(vals[j]) <= K(src[i]) } -- np.digitize(src, sorted vals), torch.bucketize(src, sorted vals, right=True);
+ *     with RSX_LOCATE_BINS_BELOW in flags, bin[i] = #{ j : K(vals[j]) < K(src[i]) } -- bucketize with right=False.  Values are
+ *     compared as bit patterns through the KDF: NaN payloads and -0.0 / +0.0 are distinct, as everywhere in this library.  The
+ *     values may come in any order and may repeat.
+ *   - Buffers: d_src and d_vals (both device memory, of the same dtype) are never written.  less and equal have room for exactly
+ *     m entries, bin for exactly n, of idx_bytes (4 or 8) each, and nothing past them is touched.  Any of the three may be NULL,
+ *     not all.  With idx_bytes == 4, n must fit where less or equal is wanted and m must fit where bin is, or the call fails with
+ *     RSX_EINVAL "does not fit".
+ *   - Trivial cases: m == 0 and no bins wanted: RSX_OK, nothing written, no device needed.  m == 0 with bins: zeros.  n == 0:
+ *     zeros in less and equal.
+ *   - Errors: bad dtype, order, idx_bytes or flags, all outputs NULL, src == NULL with n > 0, vals == NULL with m > 0: RSX_EINVAL.
+ *     Without a GPU: RSX_ENODEVICE, nothing written.  A capturing stream: RSX_EINVAL (the call waits for the number of distinct
+ *     values).  A failed allocation of the search or table route's buffers is not an error: the call takes the sort route.
+ *   - Blocking: as rsx_sort_nth_device -- the call may synchronise `stream`; the outputs are valid for work ordered after it on
+ *     `stream`; *info is complete on return.
+ * Routes (rsx_locate_info.route).  RSX_LOCATE_TABLE, keys of 1 or 2 bytes: the counts of the derived keys and of
+ * the values over the at most 2^16 derived keys, scanned; every answer is a table read.  RSX_LOCATE_SEARCH, keys of 4 or 8 bytes
+ * and at most RSX_LOCATE_MAX_SEARCH_VALUES DISTINCT values: the values are sorted and reduced to their distinct edges, a start
+ * table over the first 8 bits in which the edges differ, and the number of values at or below each edge; ONE kernel reads the
+ * keys, finds for each the number of edges at or below it (a start-table lookup and search_steps halvings in LDS), counts it in
+ * LDS and writes its bin; the counts of all workgroups, summed and scanned, are less and equal of every value.
+ * RSX_LOCATE_SORT, everything else and RSX_LOCATE_FORCE=2: a workspace copy of the keys through rsx_sort_device (none where
+ * the keys are in order already: sort.early_exit == 2) and two binary searches per value; for the bins the values sorted and
+ * one binary search per key. */
+enum { RSX_LOCATE_TRIVIAL = 0,   /* n == 0 or m == 0                                              */
+       RSX_LOCATE_TABLE   = 1,   /* 1- and 2-byte keys: count tables, scans, lookups               */
+       RSX_LOCATE_SEARCH  = 2,   /* one read of the keys against the distinct values held in LDS   */
+       RSX_LOCATE_SORT    = 3 }; /* sorts and binary searches                                      */
+enum { RSX_LOCATE_MAX_SEARCH_VALUES = 4096 };    /* more DISTINCT values than this: the sort route */
+enum { RSX_LOCATE_BINS_BELOW = 1 };              /* flags: bin[i] counts the values strictly below */
+
+typedef struct rsx_locate_info {
+	uint32_t route;            /* RSX_LOCATE_*                                                            */
+	uint32_t key_bytes;
+	uint32_t input_reads;      /* TABLE, SEARCH: kernels that read all n keys of d_src; otherwise 0        */
+	uint32_t distinct_values;  /* SEARCH: D, the distinct derived keys among vals; SORT: where the count stopped (0: not counted) */
+	uint32_t search_steps;     /* SEARCH: halvings per key behind the start table (0 .. 12)               */
+	uint32_t counter_sets;     /* SEARCH: replicas of the LDS counters per workgroup                      */
+	rsx_info sort;             /* SORT: what the inner sort of the keys reported                          */
+} rsx_locate_info;
+
+int rsx_sort_locate_device(const void *d_src, size_t n, const void *d_vals, size_t m,
+                           rsx_dtype dtype, rsx_order order,
+                           void *d_less, void *d_equal, void *d_bin, size_t idx_bytes, uint32_t flags,
+                           void *stream, rsx_locate_info *info);
+/* host or device pointers for src / vals / less / equal / bin, as rsx_sort_nth (all of the same kind) */
+int rsx_sort_locate(const void *src, size_t n, const void *vals, size_t m,
+                    rsx_dtype dtype, rsx_order order,
+                    void *less, void *equal, void *bin, size_t idx_bytes, uint32_t flags,
+                    rsx_locate_info *info);
 
 /* ---- ordering by several key columns (the stability argument one level up: README.md, "this is only possible because
  *      the sort is stable") ------------------------------------------------------------------------------------------ */

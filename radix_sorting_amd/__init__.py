@@ -96,6 +96,20 @@ class NthInfo(C.Structure):
                 ("active_buckets", C.c_uint32), ("from_prefix", C.c_uint32), ("candidates", C.c_uint64)]
 
 
+# rsx_locate_info.route, the search route's cut-off, rsx_sort_locate*'s flags
+LOCATE_TRIVIAL, LOCATE_TABLE, LOCATE_SEARCH, LOCATE_SORT = range(4)
+LOCATE_MAX_SEARCH_VALUES = 4096
+LOCATE_BINS_BELOW = 1
+# the search kernel's tile (keys) and the least number of tiles of a workgroup's share (radix_sorting_amd/csrc/rsx_locate_shape.hpp)
+LOCATE_TILE, LOCATE_SHARE_TILES = 4096, 4
+
+
+class LocateInfo(C.Structure):
+    """rsx_locate_info: the route rsx_sort_locate* took, what its search looked like and what the inner sort of the keys reported."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("input_reads", C.c_uint32), ("distinct_values", C.c_uint32),
+                ("search_steps", C.c_uint32), ("counter_sets", C.c_uint32), ("sort", Info)]
+
+
 LEX_MAX_COLS = 16
 
 
@@ -128,6 +142,7 @@ _PGINFO = C.POINTER(GroupInfo)
 _PRINFO = C.POINTER(RankdataInfo)
 _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
+_PLOCINFO = C.POINTER(LocateInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -157,6 +172,8 @@ ABI = [
     ("rsx_sort_topk", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _PTINFO]),
     ("rsx_sort_nth_device", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _VP, _PNINFO]),
     ("rsx_sort_nth", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _PNINFO]),
+    ("rsx_sort_locate_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PLOCINFO]),
+    ("rsx_sort_locate", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PLOCINFO]),
     ("rsx_sort_lex_device", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _VP, _PLINFO]),
     ("rsx_sort_lex", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _PLINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
@@ -449,6 +466,62 @@ def rankdata(src, method="ordinal", dtype=None, order=ASCENDING, idx_dtype=None,
         return le + eq - 1, info
     import torch
     return le.to(torch.float64) + (eq.to(torch.float64) - 1.0) / 2.0, info
+
+
+def radix_sort_locate(src, vals, dtype=None, order=ASCENDING, idx_dtype=None, less=True, equal=False, bins=False, below=False,
+                      stream=None):
+    """rsx_sort_locate_device: where the values ``vals`` (any order, repeats allowed, need not occur in ``src``; neither tensor is
+    written) fall in the sorted order of ``src`` by kdf(key), by BIT PATTERN (-0.0 and +0.0 are two keys):
+    ``less[j]`` keys are below ``vals[j]``, ``equal[j]`` equal it, and key i has ``bins[i]`` values at or below it
+    (``below=True``: strictly below it).
+
+    Returns (info, less, equal, bins), None for what was not asked for.  ``less`` / ``equal`` / ``bins``: True allocates the output
+    (m resp. n elements of ``idx_dtype``, default torch.int32), False leaves it out, a device tensor with room for them is
+    written in place; at least one must be wanted."""
+    import torch
+    _check_dev(src, vals)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code] or vals.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src and vals do not match the key type")
+    n, m = src.numel(), vals.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+
+    def buf(want, count, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(count, dtype=idx_dtype, device=src.device)
+        _check_dev(want)
+        if want.numel() < count or want.element_size() != idx_bytes:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    le, eq, bi = buf(less, m, "less"), buf(equal, m, "equal"), buf(bins, n, "bins")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    info = LocateInfo()
+    check(lib().rsx_sort_locate_device(src.data_ptr(), n, vals.data_ptr(), m, code, order, ptr(le), ptr(eq), ptr(bi), idx_bytes,
+                                       LOCATE_BINS_BELOW if below else 0, _stream_ptr(stream), C.byref(info)))
+    cut = lambda t, count: None if t is None else t[:count]
+    return info, cut(le, m), cut(eq, m), cut(bi, n)
+
+
+def searchsorted(src, vals, side="left", dtype=None, order=ASCENDING, idx_dtype=None, stream=None):
+    """``np.searchsorted(np.sort(src), vals, side)`` / ``torch.searchsorted(torch.sort(src).values, vals, right=side == "right")``
+    without sorting ``src`` where the values are few -- in the library's order of the keys (by bit pattern through the KDF:
+    NaNs have a place, -0.0 stands before +0.0).  Returns (positions, info)."""
+    if side not in ("left", "right"):
+        raise RsxError("searchsorted: side %r is neither 'left' nor 'right'" % (side,))
+    info, le, eq, _ = radix_sort_locate(src, vals, dtype, order, idx_dtype, less=True, equal=side == "right", stream=stream)
+    return (le if side == "left" else le + eq), info
+
+
+def bucketize(src, edges, right=False, dtype=None, order=ASCENDING, idx_dtype=None, stream=None):
+    """``torch.bucketize(src, torch.sort(edges).values, right=right)``: for every key the number of edges below it (``right=False``,
+    the library's ``below=True``) or at or below it (``right=True``: also ``np.digitize(src, np.sort(edges))``).  The edges need
+    not be sorted.  In the library's order of the keys, as searchsorted().  Returns (bins, info)."""
+    info, _, _, bi = radix_sort_locate(src, edges, dtype, order, idx_dtype, less=False, bins=True, below=not right, stream=stream)
+    return bi, info
 
 
 def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
@@ -855,6 +928,34 @@ def radix_sort_nth_host(src, ranks, dtype, order=ASCENDING, want_idx=True, idx_d
                              None if idx is None else idx.ctypes.data, 4 if idx is None else idx.itemsize, _u64p(n_less),
                              _u64p(n_equal), C.byref(info)))
     return keys, idx, n_less, n_equal, info
+
+
+def radix_sort_locate_host(src, vals, dtype, order=ASCENDING, idx_dtype=None, less=True, equal=False, bins=False, below=False):
+    """rsx_sort_locate on host numpy buffers; returns (info, less, equal, bins) as radix_sort_locate does (``idx_dtype``: a 4- or
+    8-byte numpy integer type, default uint32; an output may also be given as a numpy array with room for its elements)."""
+    import numpy as np
+    vals = np.ascontiguousarray(vals)
+    if src.itemsize != DTYPE_SIZE[dtype] or vals.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src and vals do not match the key type")
+    n, m = src.size, vals.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+
+    def buf(want, count, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(count, dtype=idx_dtype)
+        if want.size < count or want.itemsize != idx_dtype.itemsize:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    le, eq, bi = buf(less, m, "less"), buf(equal, m, "equal"), buf(bins, n, "bins")
+    ptr = lambda a: None if a is None else a.ctypes.data
+    info = LocateInfo()
+    check(lib().rsx_sort_locate(src.ctypes.data, n, vals.ctypes.data, m, dtype, order, ptr(le), ptr(eq), ptr(bi), idx_dtype.itemsize,
+                                LOCATE_BINS_BELOW if below else 0, C.byref(info)))
+    cut = lambda a, count: None if a is None else a[:count]
+    return info, cut(le, m), cut(eq, m), cut(bi, n)
 
 
 def radix_sort_lex_host(cols, dtypes, orders=None, idx_dtype=None):

@@ -25,6 +25,7 @@
 #include "rsx_rankdata.hpp"
 #include "rsx_topk.hpp"
 #include "rsx_nth.hpp"
+#include "rsx_locate.hpp"
 #include "rsx_lex.hpp"
 
 #include <hip/hip_runtime.h>
@@ -574,6 +575,7 @@ void rsx_release_stream(void *stream)
 #include "rsx_rankdata_api.hpp"  // rsx_sort_rankdata[_device]
 #include "rsx_topk_api.hpp"      // rsx_sort_topk[_device]
 #include "rsx_nth_api.hpp"       // rsx_sort_nth[_device]
+#include "rsx_locate_api.hpp"    // rsx_sort_locate[_device]
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
 
 extern "C" {

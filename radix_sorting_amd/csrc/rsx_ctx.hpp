@@ -210,6 +210,9 @@ struct Ctx {
 	DevBuf nthcand;     // ... the active buckets' (key, index) candidates and the second buffers of their sort: [keys cap] x 2 [indices cap] x 2
 	DevBuf nthio;       // ... [ranks m u64][n_less m u64][n_equal m u64][record of each position m u32]
 	DevBuf nthout;      // ... rsx_sort_nth on host buffers: the staged outputs
+	DevBuf loctab;      // rsx_sort_locate*: the search route's [header][start table][edges][cum][column totals][one row of counts per workgroup], or the table route's counts and offsets of keys and values
+	DevBuf locvals;     // ... [values m][values m]: a copy of the values and the second buffer of its sort
+	DevBuf locout;      // ... rsx_sort_locate on host buffers: the staged values and the staged outputs
 	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
 	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
 	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
@@ -327,6 +330,9 @@ struct Ctx {
 		nthcand.release();
 		nthio.release();
 		nthout.release();
+		loctab.release();
+		locvals.release();
+		locout.release();
 		lexkeys.release();
 		lexidx.release();
 		lexstage.release();

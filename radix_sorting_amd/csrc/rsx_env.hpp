@@ -20,6 +20,8 @@ enum : unsigned { UNIQUE_MAX_BITS_COMPILED = 30, UNIQUE_MAX_BITS_DEFAULT = 24 };
 enum : unsigned { GROUP_MAX_BITS_COMPILED = 30, GROUP_MAX_BITS_DEFAULT = 24 };
 // rsx_sort_lex*: neighbouring columns are packed into one key of at most this many bytes
 enum : unsigned { LEX_PACK_BYTES_DEFAULT = 4 };
+// rsx_sort_locate*: the search route takes at most this many distinct values
+enum : unsigned { LOCATE_MAX_VALUES_DEFAULT = 4096 };
 struct Env {
 	bool host_register = false;      // RSX_HOST_REGISTER=1
 	bool force_table_rank = false;   // RSX_FORCE_TABLE_RANK=1
@@ -78,6 +80,9 @@ struct Env {
 	bool rankdata_no_tables = false; // RSX_RANKDATA_NO_TABLES=1 (tests, probe): rsx_sort_rankdata* always takes the sort route (no column table, no count table)
 	unsigned nth_force = 0;          // RSX_NTH_FORCE=1: rsx_sort_nth* selects whenever n >= 2 and 1 <= distinct ranks <= 64; =2: always the sort route
 	unsigned topk_force = 0;         // RSX_TOPK_FORCE=1: rsx_sort_topk* selects whenever n >= 2 and 0 < k <= n; =2: always the sort route
+	unsigned locate_force = 0;       // RSX_LOCATE_FORCE=2: rsx_sort_locate* always takes the sort route
+	unsigned locate_max_values = LOCATE_MAX_VALUES_DEFAULT;   // RSX_LOCATE_MAX_VALUES=k (1 .. 4096; tests): rsx_sort_locate* searches while there are at most k distinct values
+	unsigned locate_counter_sets = 0; // RSX_LOCATE_COUNTER_SETS=k (tests, probe): the search kernel keeps k sets of LDS counters (0: as many as fit, at most 32)
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
 	// What a variable's text means.  An absent variable leaves the member's default initialiser, which load() restores first:
 	// rsx_reload_env() after a test has taken its variable away is back at the default.
@@ -162,6 +167,9 @@ struct Env {
 		rankdata_no_tables = is_one("RSX_RANKDATA_NO_TABLES");
 		topk_force = one_or_two("RSX_TOPK_FORCE");
 		nth_force = one_or_two("RSX_NTH_FORCE");
+		locate_force = one_or_two("RSX_LOCATE_FORCE");
+		within("RSX_LOCATE_MAX_VALUES", &locate_max_values, 1, (int)LOCATE_MAX_VALUES_DEFAULT);
+		within("RSX_LOCATE_COUNTER_SETS", &locate_counter_sets, 1, 32);
 		within("RSX_LEX_PACK_BYTES", &lex_pack_bytes, 1, 8);
 		number("RSX_UNIQUE_MAX_BITS", &unique_max_bits, 0, (int)UNIQUE_MAX_BITS_COMPILED);
 		number("RSX_GROUP_MAX_BITS", &group_max_bits, 0, (int)GROUP_MAX_BITS_COMPILED);
