@@ -317,6 +317,39 @@ size_t radix_sort_group(const T *src, IdxType *inverse, size_t n, T *keys = null
 	return n_groups;
 }
 
+// Not in the reference's header (radix_sort_group one step further): per group of bit-equal keys, in order of kf(key), what
+// thrust::reduce_by_key or pandas' groupby(k).agg(["count", "sum", "min", "max"]) return for a second column.  keys and vals
+// (n each) are not written.  If given (room for n each): the distinct keys into out_keys, how many of each into counts, the
+// sum of each group's values into sum -- 64 bits wide: uint64_t / int64_t modulo 2^64 for integer V, double for float and double
+// -- and its smallest / largest value into min / max, by the value's own KDF (floats by bit pattern: -0.0 below +0.0, a NaN with
+// the sign bit clear above +inf; a NaN does not poison them).  Returns the number of groups (rsx_sort_reduce).  V is a 4- or
+// 8-byte arithmetic type; scalar T with basic_kdfs::kdf or rsx_kdf::descending<T>.
+namespace rsx_detail {
+template <typename V>
+using reduce_sum_t = std::conditional_t<std::is_floating_point_v<V>, double, std::conditional_t<std::is_signed_v<V>, int64_t, uint64_t>>;
+}
+
+template <typename T, typename V, typename IdxType = uint32_t, typename KeyFunc = decltype(basic_kdfs::kdf<T>)>
+size_t radix_sort_reduce(const T *keys, const V *vals, size_t n, T *out_keys = nullptr, IdxType *counts = nullptr,
+                         rsx_detail::reduce_sum_t<V> *sum = nullptr, V *min = nullptr, V *max = nullptr, KeyFunc &&kf = basic_kdfs::kdf<T>)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, KeyFunc> || rsx_detail::is_descending_kdf_v<T, KeyFunc>,
+	              "radix_sort_reduce takes scalar keys with basic_kdfs::kdf or rsx_kdf::descending");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_reduce: IdxType of 4 or 8 bytes");
+	static_assert(std::is_arithmetic_v<V> && (sizeof(V) == 4 || sizeof(V) == 8), "radix_sort_reduce: values of 4 or 8 bytes");
+	if constexpr (rsx_detail::may_be_default_kdf_v<T, KeyFunc>)
+		if (!rsx_detail::kdf_kind<T, KeyFunc>::is_default(kf))
+			throw std::invalid_argument("radix_sort_reduce: a function other than basic_kdfs::kdf<T> was passed as KeyFunc");
+	size_t n_groups = 0;
+	const unsigned ops = (sum ? RSX_REDUCE_SUM : 0) | (min ? RSX_REDUCE_MIN : 0) | (max ? RSX_REDUCE_MAX : 0);
+	const int rc = rsx_sort_reduce(keys, vals, n, rsx_detail::dtype_of<T>(),
+	                               rsx_detail::is_descending_kdf_v<T, KeyFunc> ? RSX_DESCENDING : RSX_ASCENDING, rsx_detail::dtype_of<V>(), ops,
+	                               out_keys, counts, sizeof(IdxType), sum, min, max, &n_groups, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_reduce", rc);
+	return n_groups;
+}
+
 // Not in the reference's header (its README's counting sort read per key): for every element of src, which is not written,
 // where it stands in the stable sorted order by kf(element) into place -- the inverse of radix_sort_rank's permutation, what
 // argsort(argsort(x)) returns -- and, if given, how many elements have a smaller derived key into less and how many an equal

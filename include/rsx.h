@@ -152,6 +152,14 @@
  *                           as fit, at most 32);
  *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
  *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
+ *   RSX_REDUCE_MAX_BITS=k   rsx_sort_reduce*: the cells routes while at most k bits of the derived keys vary, k in 0 .. 24 (default 12,
+ *                           the LDS cut-off: beyond it the cells in device memory lost to the sort in every measured row, DESIGN.md
+ *                           4o); 0: never cells -- everything goes through the sort and the runs pass;
+ *   RSX_REDUCE_LDS_BITS=k   rsx_sort_reduce*: the cells lie in LDS while at most k bits vary, k in 0 .. 12 (default 12); beyond that,
+ *                           up to RSX_REDUCE_MAX_BITS, in device memory;
+ *   RSX_REDUCE_REPLICAS=k   (tests, probe) the cells kernel keeps k copies of its LDS cells, k in 1 .. 32 brought down to a power
+ *                           of two that fits (default: as many as fit, at most 32);
+ *   RSX_REDUCE_FORCE=2      rsx_sort_reduce*: always the sort route (tests run both and compare; tools/reduce_probe.py times both);
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
  */
 #ifndef RSX_H
@@ -685,6 +693,66 @@ int rsx_sort_lex_device(const rsx_lex_col *cols, size_t ncols, size_t n, void *d
                         void *stream, rsx_lex_info *info);
 /* host or device pointers, as rsx_sort (all of the same kind); host columns are staged, each distinct one once */
 int rsx_sort_lex(const rsx_lex_col *cols, size_t ncols, size_t n, void *out_idx, size_t idx_bytes, rsx_lex_info *info);
+
+/* ---- per-group count, sum, min and max of a second column (reduce_by_key over rsx_sort_unique's groups) -------------- */
+
+/* For every group of equal keys -- the groups of rsx_sort_group, in rsx_sort_unique's order -- how many elements it has and the
+ * sum, the smallest and the largest of the values that stand beside its keys.
+ * Let U[0 .. G) be what rsx_sort_unique returns for the same keys, dtype and order (distinct BIT PATTERNS, ascending by kdf(key);
+ * RSX_DESCENDING: by the complemented KDF).  *n_groups = G, and for j < G:
+ *   - out_keys[j] = U[j]; out_counts[j] = the size of group j, idx_bytes (4 or 8) wide; with 4, n must fit, or the call fails
+ *     with RSX_EINVAL "does not fit".
+ *   - out_sum[j], always 8 bytes wide: integer values (RSX_U32, RSX_I32, RSX_U64, RSX_I64) are zero- or sign-extended to 64 bits
+ *     and added modulo 2^64 -- a u64 / i64 bit pattern, exact whatever the order of the additions.  RSX_F32 / RSX_F64 values are
+ *     converted to f64 (exact) and added with IEEE double additions, starting from +0.0, in an order the call does not specify
+ *     (on the sort route it is the same from run to run); infinities and NaNs propagate as the additions make them.
+ *   - out_min[j] / out_max[j], in val_dtype: the value of the group whose kdf(value) under val_dtype and RSX_ASCENDING is
+ *     smallest / largest, whatever `order` says about the keys.  That is numeric order for integers; for floats it is the float
+ *     KDF's total order on BIT PATTERNS: -0.0 < +0.0, NaNs with the sign bit clear above +inf, NaNs with it set below -inf.
+ *     This is the library's "keys are bit patterns" rule, NOT numpy's NaN propagation: a NaN does not poison min or max.
+ *   - val_dtype is one of the six 4- and 8-byte dtypes; a narrower one: RSX_EINVAL.
+ *   - ops: bits of RSX_REDUCE_SUM | RSX_REDUCE_MIN | RSX_REDUCE_MAX.  Every output may be NULL, each on its own, but sum, min
+ *     and max must agree with their bit: a bit whose output is NULL, or an output whose bit is clear: RSX_EINVAL.  ops == 0 with
+ *     only keys or counts wanted is legal.  n_groups is required, and with n > 0 so are d_keys and d_vals.
+ *   - Buffers: d_keys and d_vals are never written.  Each output has room for n entries and nothing outside [0, n) of any of
+ *     them is touched; entries at or past G are unspecified.
+ *   - Errors: bad dtype, order, val_dtype, ops or idx_bytes, NULL n_groups: RSX_EINVAL.  n == 0: RSX_OK, *n_groups = 0, nothing
+ *     written, no device needed.  n == 1: rsx_sort_reduce on host pointers needs no device, rsx_sort_reduce_device only for the
+ *     copies.  Otherwise, without a GPU: RSX_ENODEVICE, nothing written.  A capturing stream: RSX_EINVAL (the call waits for the
+ *     number of groups).  A failed allocation of the table of cells is not an error: the call takes the sort route.
+ *   - Blocking: as rsx_sort_group_device.
+ * The route is chosen from what the call can observe of the keys (rsx_reduce_info.route).  Where at most
+ * RSX_REDUCE_LDS_BITS (12) bits of the derived keys vary -- category codes, one byte column, all 1-byte keys -- the packed
+ * varying bits number a cell per possible key, every workgroup accumulates its share of keys and values into copies of the
+ * cells in its LDS, merges them into one table, and the table is read out in order: one streaming read, nothing sorted, no
+ * inverse.  Up to RSX_REDUCE_MAX_BITS the same with the cells in device memory -- off by default (RSX_REDUCE_MAX_BITS = 12): it
+ * lost to the sort route wherever it was measured.  Everything else is a stable key + value sort
+ * of workspace copies (rsx_sort_pairs_device's routes; none where the input is sorted already) and a segmented reduction over
+ * the runs of its result.  Memory, in the (device, stream) context: the table (at most 32 bytes per cell), or copies of keys
+ * and values with their second buffers and 80 bytes per tile of the sorted array; freed by rsx_release / rsx_release_stream. */
+enum { RSX_REDUCE_SUM = 1, RSX_REDUCE_MIN = 2, RSX_REDUCE_MAX = 4 };          /* bits of `ops` */
+enum { RSX_REDUCE_TRIVIAL = 0,       /* n < 2, or every key equal                                             */
+       RSX_REDUCE_CELLS_LDS = 1,     /* one read of keys + values into per-packed-value accumulators in LDS   */
+       RSX_REDUCE_CELLS_GLOBAL = 2,  /* the same body, the accumulators in device memory                      */
+       RSX_REDUCE_SORT = 3 };        /* stable key + value sort (any route), heads, one pass over the runs    */
+typedef struct rsx_reduce_info {
+	rsx_info sort;          /* as rsx_unique_info.sort */
+	uint32_t route;         /* RSX_REDUCE_* */
+	uint32_t varying_bits;  /* popcount of the KDF bits that differ among the keys; 0 = not computed */
+	uint64_t table_bytes;   /* the table of cells used, 0 otherwise */
+} rsx_reduce_info;
+
+int rsx_sort_reduce_device(const void *d_keys, const void *d_vals, size_t n, rsx_dtype dtype, rsx_order order,
+                           rsx_dtype val_dtype, unsigned ops,
+                           void *d_out_keys, void *d_out_counts, size_t idx_bytes,
+                           void *d_out_sum, void *d_out_min, void *d_out_max,
+                           void *stream, size_t *n_groups, rsx_reduce_info *info);
+/* host or device pointers, as rsx_sort (all of the same kind); host keys and values are staged side by side */
+int rsx_sort_reduce(const void *keys, const void *vals, size_t n, rsx_dtype dtype, rsx_order order,
+                    rsx_dtype val_dtype, unsigned ops,
+                    void *out_keys, void *out_counts, size_t idx_bytes,
+                    void *out_sum, void *out_min, void *out_max,
+                    size_t *n_groups, rsx_reduce_info *info);
 
 /* ---- key + payload (struct-of-arrays) ------------------------------------- */
 

@@ -66,6 +66,16 @@ class GroupInfo(C.Structure):
     _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
 
 
+# rsx_reduce_info.route, the bits of rsx_sort_reduce*'s ops
+REDUCE_TRIVIAL, REDUCE_CELLS_LDS, REDUCE_CELLS_GLOBAL, REDUCE_SORT = range(4)
+REDUCE_SUM, REDUCE_MIN, REDUCE_MAX = 1, 2, 4
+
+
+class ReduceInfo(C.Structure):
+    """rsx_reduce_info: the route rsx_sort_reduce* took and what the front half of the sort decided."""
+    _fields_ = [("sort", Info), ("route", C.c_uint32), ("varying_bits", C.c_uint32), ("table_bytes", C.c_uint64)]
+
+
 # rsx_rankdata_info.route
 RANKDATA_TRIVIAL, RANKDATA_TABLE, RANKDATA_COUNT16, RANKDATA_SORT = range(4)
 
@@ -140,6 +150,7 @@ _PUINFO, _PSZ = C.POINTER(UniqueInfo), C.POINTER(C.c_size_t)
 _PTINFO = C.POINTER(TopkInfo)
 _PGINFO = C.POINTER(GroupInfo)
 _PRINFO = C.POINTER(RankdataInfo)
+_PREDINFO = C.POINTER(ReduceInfo)
 _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 _PLOCINFO = C.POINTER(LocateInfo)
@@ -166,6 +177,8 @@ ABI = [
     ("rsx_sort_unique", _I, [_VP, _VP, _SZ, _I, _I, _VP, _SZ, _PVP, _PSZ, _PUINFO]),
     ("rsx_sort_group_device", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _VP, _PSZ, _PGINFO]),
     ("rsx_sort_group", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _VP, _SZ, _PSZ, _PGINFO]),
+    ("rsx_sort_reduce_device", _I, [_VP, _VP, _SZ, _I, _I, _I, C.c_uint, _VP, _VP, _SZ, _VP, _VP, _VP, _VP, _PSZ, _PREDINFO]),
+    ("rsx_sort_reduce", _I, [_VP, _VP, _SZ, _I, _I, _I, C.c_uint, _VP, _VP, _SZ, _VP, _VP, _VP, _PSZ, _PREDINFO]),
     ("rsx_sort_rankdata_device", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _VP, _PRINFO]),
     ("rsx_sort_rankdata", _I, [_VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _PRINFO]),
     ("rsx_sort_topk_device", _I, [_VP, _SZ, _SZ, _I, _I, _VP, _VP, _SZ, _VP, _PTINFO]),
@@ -402,6 +415,60 @@ def radix_sort_group(src, dtype=None, order=ASCENDING, idx_dtype=None, keys=Fals
     g = ng.value
     cut = lambda t: None if t is None else t[:g]
     return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
+
+
+def _reduce_ops(sum_buf, min_buf, max_buf):
+    return (REDUCE_SUM if sum_buf is not None else 0) | (REDUCE_MIN if min_buf is not None else 0) | (REDUCE_MAX if max_buf is not None else 0)
+
+
+def radix_sort_reduce(keys, vals, dtype=None, val_dtype=None, order=ASCENDING, idx_dtype=None, sum=True, min=False, max=False,
+                      counts=False, keys_out=True, stream=None):
+    """rsx_sort_reduce_device: per group of bit-equal ``keys`` (not written), in order of kdf(key), the number of elements and
+    the sum, the smallest and the largest of the ``vals`` (not written; 4- or 8-byte elements) that stand beside them -- what
+    ``torch.unique(return_inverse=True)`` + ``index_add_`` / ``scatter_reduce``, ``np.bincount(k, weights=v)`` or a COO
+    ``coalesce()`` compute.
+
+    Returns (keys[:G] or None, counts[:G] or None, sum[:G] or None, min[:G] or None, max[:G] or None, info).  ``sum`` is 64 bits
+    wide: int64 holding the u64 / i64 sum modulo 2^64 for integer values, float64 for float values.  ``min`` / ``max`` are in the
+    values' type, ordered by the value's own KDF (floats by bit pattern: -0.0 below +0.0, a NaN with the sign bit clear above
+    +inf: a NaN does not poison them).  Each of ``keys_out`` / ``counts`` / ``sum`` / ``min`` / ``max``: True allocates the output
+    (n elements; ``idx_dtype``, default torch.int32, for the counts), False leaves it out, a device tensor with room for n elements
+    is written in place.  The call returns once G is known."""
+    import torch
+    _check_dev(keys, vals)
+    code = _torch_dtype_code(keys) if dtype is None else dtype
+    vcode = _torch_dtype_code(vals) if val_dtype is None else val_dtype
+    if keys.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("keys do not match the key type")
+    if vals.element_size() != DTYPE_SIZE[vcode] or vals.numel() < keys.numel():
+        raise RsxError("vals do not match the value type or the keys")
+    n = keys.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+    sum_dtype = torch.float64 if vcode in (F32, F64) else torch.int64
+
+    def buf(want, what, dt, size):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(n, dtype=dt, device=keys.device)
+        _check_dev(want)
+        if want.numel() < n or want.element_size() != size:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    k = buf(keys_out, "keys_out", keys.dtype, keys.element_size())
+    cn = buf(counts, "counts", idx_dtype, idx_bytes)
+    sm = buf(sum, "sum", sum_dtype, 8)
+    mn = buf(min, "min", vals.dtype, vals.element_size())
+    mx = buf(max, "max", vals.dtype, vals.element_size())
+    ptr = lambda t: None if t is None else t.data_ptr()
+    ng, info = C.c_size_t(0), ReduceInfo()
+    check(lib().rsx_sort_reduce_device(keys.data_ptr(), vals.data_ptr(), n, code, order, vcode, _reduce_ops(sm, mn, mx), ptr(k), ptr(cn),
+                                       idx_bytes, ptr(sm), ptr(mn), ptr(mx), _stream_ptr(stream), C.byref(ng), C.byref(info)))
+    g = ng.value
+    cut = lambda t: None if t is None else t[:g]
+    return cut(k), cut(cn), cut(sm), cut(mn), cut(mx), info
 
 
 def radix_sort_rankdata(src, dtype=None, order=ASCENDING, idx_dtype=None, place=True, less=False, equal=False, stream=None):
@@ -869,6 +936,39 @@ def radix_sort_group_host(src, dtype, order=ASCENDING, idx_dtype=None, keys=Fals
     g = ng.value
     cut = lambda a: None if a is None else a[:g]
     return (None if inv is None else inv[:n]), cut(k), cut(cn), cut(fi), info
+
+
+def radix_sort_reduce_host(keys, vals, dtype, val_dtype, order=ASCENDING, idx_dtype=None, sum=True, min=False, max=False, counts=False,
+                           keys_out=True):
+    """rsx_sort_reduce on host numpy buffers; returns (keys[:G], counts[:G], sum[:G], min[:G], max[:G], info), None where one was
+    not asked for, as radix_sort_reduce does (``idx_dtype``: a 4- or 8-byte numpy integer type, default uint32; ``sum`` comes as
+    uint64 bit patterns for integer values and float64 for float values; an output may also be given as a numpy array with room
+    for n elements)."""
+    import numpy as np
+    if keys.itemsize != DTYPE_SIZE[dtype] or vals.itemsize != DTYPE_SIZE[val_dtype] or vals.size < keys.size:
+        raise RsxError("keys / vals do not match their types")
+    n = keys.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+    sum_dtype = np.float64 if val_dtype in (F32, F64) else np.uint64
+
+    def buf(want, what, dt):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(n, dtype=dt)
+        if want.size < n or want.itemsize != np.dtype(dt).itemsize:
+            raise RsxError("%s must have room for n elements of the right size" % what)
+        return want
+
+    k, cn, sm = buf(keys_out, "keys_out", keys.dtype), buf(counts, "counts", idx_dtype), buf(sum, "sum", sum_dtype)
+    mn, mx = buf(min, "min", vals.dtype), buf(max, "max", vals.dtype)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    ng, info = C.c_size_t(0), ReduceInfo()
+    check(lib().rsx_sort_reduce(keys.ctypes.data, vals.ctypes.data, n, dtype, order, val_dtype, _reduce_ops(sm, mn, mx), ptr(k), ptr(cn),
+                                idx_dtype.itemsize, ptr(sm), ptr(mn), ptr(mx), C.byref(ng), C.byref(info)))
+    g = ng.value
+    cut = lambda a: None if a is None else a[:g]
+    return cut(k), cut(cn), cut(sm), cut(mn), cut(mx), info
 
 
 def radix_sort_rankdata_host(src, dtype, order=ASCENDING, idx_dtype=None, place=True, less=False, equal=False):

@@ -27,6 +27,7 @@
 #include "rsx_nth.hpp"
 #include "rsx_locate.hpp"
 #include "rsx_lex.hpp"
+#include "rsx_reduce.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -577,6 +578,7 @@ void rsx_release_stream(void *stream)
 #include "rsx_nth_api.hpp"       // rsx_sort_nth[_device]
 #include "rsx_locate_api.hpp"    // rsx_sort_locate[_device]
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
+#include "rsx_reduce_api.hpp"    // rsx_sort_reduce[_device]
 
 extern "C" {
 

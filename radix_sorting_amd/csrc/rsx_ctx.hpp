@@ -213,6 +213,8 @@ struct Ctx {
 	DevBuf loctab;      // rsx_sort_locate*: the search route's [header][start table][edges][cum][column totals][one row of counts per workgroup], or the table route's counts and offsets of keys and values
 	DevBuf locvals;     // ... [values m][values m]: a copy of the values and the second buffer of its sort
 	DevBuf locout;      // ... rsx_sort_locate on host buffers: the staged values and the staged outputs
+	DevBuf rcells;      // rsx_sort_reduce*: the table of cells [counts][sums][minima][maxima], or a ReducePart per tile of the sorted array
+	DevBuf rout;        // ... rsx_sort_reduce on host buffers: the staged outputs
 	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
 	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
 	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
@@ -333,6 +335,8 @@ struct Ctx {
 		loctab.release();
 		locvals.release();
 		locout.release();
+		rcells.release();
+		rout.release();
 		lexkeys.release();
 		lexidx.release();
 		lexstage.release();

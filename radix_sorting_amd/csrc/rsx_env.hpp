@@ -22,6 +22,9 @@ enum : unsigned { GROUP_MAX_BITS_COMPILED = 30, GROUP_MAX_BITS_DEFAULT = 24 };
 enum : unsigned { LEX_PACK_BYTES_DEFAULT = 4 };
 // rsx_sort_locate*: the search route takes at most this many distinct values
 enum : unsigned { LOCATE_MAX_VALUES_DEFAULT = 4096 };
+// rsx_sort_reduce*: the widest table of cells the library was compiled for (in LDS, in device memory) and the widest it takes by
+// default -- the LDS cut-off: the cells in device memory lost to the sort route in every measured row
+enum : unsigned { REDUCE_LDS_BITS_COMPILED = 12, REDUCE_MAX_BITS_COMPILED = 24, REDUCE_MAX_BITS_DEFAULT = 12 };
 struct Env {
 	bool host_register = false;      // RSX_HOST_REGISTER=1
 	bool force_table_rank = false;   // RSX_FORCE_TABLE_RANK=1
@@ -83,6 +86,10 @@ struct Env {
 	unsigned locate_force = 0;       // RSX_LOCATE_FORCE=2: rsx_sort_locate* always takes the sort route
 	unsigned locate_max_values = LOCATE_MAX_VALUES_DEFAULT;   // RSX_LOCATE_MAX_VALUES=k (1 .. 4096; tests): rsx_sort_locate* searches while there are at most k distinct values
 	unsigned locate_counter_sets = 0; // RSX_LOCATE_COUNTER_SETS=k (tests, probe): the search kernel keeps k sets of LDS counters (0: as many as fit, at most 32)
+	unsigned reduce_max_bits = REDUCE_MAX_BITS_DEFAULT;   // RSX_REDUCE_MAX_BITS=k (0 .. 24): rsx_sort_reduce* accumulates into cells while at most k bits of the keys vary (0: never)
+	unsigned reduce_lds_bits = REDUCE_LDS_BITS_COMPILED;  // RSX_REDUCE_LDS_BITS=k (0 .. 12): ... and keeps the cells in LDS while at most k do (beyond: in device memory)
+	unsigned reduce_replicas = 0;    // RSX_REDUCE_REPLICAS=k (tests, probe): the cells kernel keeps k copies of the cells in LDS (0: as many as fit, at most 32)
+	unsigned reduce_force = 0;       // RSX_REDUCE_FORCE=2: rsx_sort_reduce* always takes the sort route
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
 	// What a variable's text means.  An absent variable leaves the member's default initialiser, which load() restores first:
 	// rsx_reload_env() after a test has taken its variable away is back at the default.
@@ -171,6 +178,10 @@ struct Env {
 		within("RSX_LOCATE_MAX_VALUES", &locate_max_values, 1, (int)LOCATE_MAX_VALUES_DEFAULT);
 		within("RSX_LOCATE_COUNTER_SETS", &locate_counter_sets, 1, 32);
 		within("RSX_LEX_PACK_BYTES", &lex_pack_bytes, 1, 8);
+		number("RSX_REDUCE_MAX_BITS", &reduce_max_bits, 0, (int)REDUCE_MAX_BITS_COMPILED);
+		number("RSX_REDUCE_LDS_BITS", &reduce_lds_bits, 0, (int)REDUCE_LDS_BITS_COMPILED);
+		within("RSX_REDUCE_REPLICAS", &reduce_replicas, 1, 32);
+		reduce_force = one_or_two("RSX_REDUCE_FORCE");
 		number("RSX_UNIQUE_MAX_BITS", &unique_max_bits, 0, (int)UNIQUE_MAX_BITS_COMPILED);
 		number("RSX_GROUP_MAX_BITS", &group_max_bits, 0, (int)GROUP_MAX_BITS_COMPILED);
 		within("RSX_TWO_LEVEL_MIN_LOG2", &two_level_min_log2, 22, 30);
