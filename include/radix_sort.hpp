@@ -420,6 +420,41 @@ void radix_sort_locate(const T *src, size_t n, const T *vals, size_t m, IdxType 
 		rsx_detail::fail("radix_sort_locate", rc);
 }
 
+// Not in the reference's header: the equi-join of two key columns, neither of which is written, in two steps (rsx_sort_join,
+// rsx_join_pairs).  radix_sort_join finds, for every row of `left`, its range into the stable sorted order of `right`:
+// right_perm (room for m) = that order, count[i] (room for n) = the rows of right whose derived key equals left[i]'s, and
+// where count[i] > 0 they are right_perm[start[i] .. start[i] + count[i]) (start: room for n; unspecified where count[i] == 0).
+// Any of the three may be nullptr.  Returns the number of pairs: the sum of the counts, with flags = RSX_JOIN_LEFT of
+// max(count, 1).  By bit pattern through basic_kdfs::kdf; RSX_DESCENDING for the complemented order.
+template <typename IdxType, typename T>
+uint64_t radix_sort_join(const T *left, size_t n, const T *right, size_t m, IdxType *start, IdxType *count, IdxType *right_perm,
+                         rsx_order order = RSX_ASCENDING, uint32_t flags = 0)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_join takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_join: IdxType of 4 or 8 bytes");
+	uint64_t n_pairs = 0;
+	const int rc = rsx_sort_join(left, n, right, m, rsx_detail::dtype_of<T>(), order, start, count, right_perm, sizeof(IdxType), flags, &n_pairs, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_join", rc);
+	return n_pairs;
+}
+
+// ... and radix_sort_join_pairs expands such ranges into the pairs, ordered by left row, then by right row: out_left[p] = i,
+// out_right[p] = the t-th entry of row i's range (flags = RSX_JOIN_LEFT: a row without a match yields one pair whose right index
+// is IdxType(-1)).  Each output has room for `capacity` entries; either may be nullptr, not both.  Returns the number of pairs;
+// more than `capacity` is an error (std::runtime_error) and nothing is written.
+template <typename IdxType>
+uint64_t radix_sort_join_pairs(const IdxType *start, const IdxType *count, const IdxType *right_perm, size_t n, size_t m, IdxType *out_left,
+                               IdxType *out_right, uint64_t capacity, uint32_t flags = 0)
+{
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_join_pairs: IdxType of 4 or 8 bytes");
+	uint64_t n_pairs = 0;
+	const int rc = rsx_join_pairs(start, count, right_perm, n, m, sizeof(IdxType), flags, out_left, out_right, capacity, &n_pairs);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_join_pairs", rc);
+	return n_pairs;
+}
+
 // Not in the reference's header (its text's stability argument one level up): the stable argsort of n rows by several key
 // columns, none of which is written, into idx_out (room for n).  c0 is the MOST significant column, as in ORDER BY c0, c1, ...
 // (np.lexsort takes its keys in the reverse order); rows equal in every column come in ascending index order.  Scalar column

@@ -79,6 +79,12 @@
  *   workspace); rsx_sort_locate on host buffers also the staged keys, values and outputs.  Freed by rsx_release /
  *   rsx_release_stream, never allocated inside a stream capture (the call refuses a capturing stream).  If an allocation of
  *   the search or table route fails the call takes the sort route.
+ *   rsx_sort_join*, rsx_join_pairs*: in the (device, stream) context: the table route's counts and offsets of the right keys
+ *   (768 KiB) and two sums per workgroup of its probe; what rsx_sort_pairs / rsx_sort keeps for a copy of the right keys (2 m
+ *   keys, 2 m indices where right_perm is wanted); the merge route the same for the left side plus 2 n indices; n indices where
+ *   count is not asked for; 8 bytes per RSX_JOIN_ROW_TILE rows for the expansion; on host buffers also the staged keys, inputs and
+ *   outputs.  Freed by rsx_release / rsx_release_stream, never allocated inside a stream capture (the calls refuse a capturing
+ *   stream).  If the allocation of the table fails the call takes the general route.
  *
  * Environment switches (read ONCE, at the library's first call; rsx_reload_env() reads them again)
  *   RSX_VERIFY=1            after every scatter pass one tile is re-ranked without LDS
@@ -160,6 +166,9 @@
  *   RSX_REDUCE_REPLICAS=k   (tests, probe) the cells kernel keeps k copies of its LDS cells, k in 1 .. 32 brought down to a power
  *                           of two that fits (default: as many as fit, at most 32);
  *   RSX_REDUCE_FORCE=2      rsx_sort_reduce*: always the sort route (tests run both and compare; tools/reduce_probe.py times both);
+ *   RSX_JOIN_FORCE=2|3      rsx_sort_join*: 2: always the search route (the left keys as they come), 3: always the merge route (the
+ *                           left side sorted too); tests run both and compare, tools/join_probe.py times both;
+ *   RSX_JOIN_NO_TABLE=1     rsx_sort_join*: never the table route;
  *   RSX_COMPACT_BITS=1, RSX_HOST_REGISTER=1, RSX_ELEM_LOADS=1   opt-in variants.
  */
 #ifndef RSX_H
@@ -753,6 +762,93 @@ int rsx_sort_reduce(const void *keys, const void *vals, size_t n, rsx_dtype dtyp
                     void *out_keys, void *out_counts, size_t idx_bytes,
                     void *out_sum, void *out_min, void *out_max,
                     size_t *n_groups, rsx_reduce_info *info);
+
+/* ---- matching rows of two key columns: the equi-join (pandas.merge, SQL JOIN ... ON a.k = b.k, np.intersect1d with indices,
+ *      isin, the symbolic phase of a sparse product, gathering a dimension table's rows into a fact table) ------------------------ */
+
+/* Two calls.  Phase 1, rsx_sort_join*, writes the join in compressed form -- one range into the sorted right side per left row --
+ * and says how many pairs there are; phase 2, rsx_join_pairs*, expands such ranges into the two lists of row numbers.
+ * Let K(x) be the derived key of x under dtype and order (the KDF, complemented for RSX_DESCENDING), compared as a BIT PATTERN as
+ * everywhere in this library: -0.0 and +0.0 differ, a NaN equals itself exactly when its bits do.  left has n rows, right has m,
+ * both of `dtype`; P is the stable argsort of right under K (what rsx_sort_rank returns for it).
+ * Phase 1:
+ *   - right_perm[0 .. m) = P.  For every i < n: count[i] = #{ j : K(right[j]) == K(left[i]) }, and WHERE count[i] > 0,
+ *     start[i] = #{ j : K(right[j]) < K(left[i]) }: the matches of row i are P[start[i] .. start[i] + count[i]), in ascending j.
+ *     Where count[i] == 0, start[i] is written but its value is unspecified (the table route cannot order a key that differs
+ *     from every right key in a bit that does not vary among them, and no use of the join needs the value).
+ *   - *n_pairs = the sum of count[i]; with RSX_JOIN_LEFT in flags the sum of max(count[i], 1).  It is a uint64_t whatever
+ *     idx_bytes is: the pairs of 2^17 rows against 2^16 may number 2^33.
+ *   - Buffers: d_left and d_right are never written.  start and count have room for exactly n entries, right_perm for exactly m,
+ *     of idx_bytes (4 or 8) each, and nothing past them is touched.  Each of the three may be NULL, and all three may be (only
+ *     the number of pairs is wanted).  With idx_bytes == 4, n and m must fit, or the call fails with RSX_EINVAL "does not fit".
+ *   - Trivial cases: n == 0 or m == 0: route RSX_JOIN_TRIVIAL, count is zeros (start too), right_perm an iota, *n_pairs = 0 (n under
+ *     RSX_JOIN_LEFT); no device is needed where that leaves nothing to write, and rsx_sort_join on host pointers never needs one
+ *     for it.
+ *   - Errors: bad dtype, order, idx_bytes or flags, NULL n_pairs, left == NULL with n > 0, right == NULL with m > 0: RSX_EINVAL.
+ *     Without a GPU: RSX_ENODEVICE, nothing written.  A capturing stream: RSX_EINVAL (the call waits for the number of pairs).
+ *     A failed allocation of the table is not an error: the call takes the general route.
+ *   - Blocking: as rsx_sort_locate_device -- the call may synchronise `stream`; the outputs are valid for work ordered after it
+ *     on `stream`; *n_pairs and *info are complete on return.
+ * Routes of phase 1 (rsx_join_info.route), chosen from what the call can observe of the RIGHT keys; the left keys are
+ * never inspected beforehand.  RSX_JOIN_TABLE, direct addressing: at most 16 bits of the right keys vary, in at most eight runs,
+ * and m < 2^32 (all 1-byte keys qualify): the right keys' packed varying bits are counted and scanned, and ONE kernel streams
+ * the left keys, tests each against the right keys' non-varying bits and reads two neighbouring offsets of the table; the right
+ * side is sorted only where right_perm is wanted.  RSX_JOIN_SEARCH: the right side is sorted (key + iota, or keys alone where
+ * right_perm is not wanted; nothing is copied or sorted where the keys are in order already: sort.early_exit == 2 and right_perm
+ * an iota) and the left keys are searched in it as they come.  RSX_JOIN_MERGE: the same, but the left side is sorted too (key +
+ * iota), the search runs over the SORTED left keys so that neighbouring lanes search neighbouring places, and start / count go
+ * back through the left permutation (left_sorted = 1).  RSX_JOIN_FORCE=2 / =3 forces SEARCH / MERGE, RSX_JOIN_NO_TABLE=1 closes
+ * TABLE.
+ * Phase 2, rsx_join_pairs*, reads only arrays as phase 1 wrote them -- no keys, no sort, no state kept between the calls:
+ *   - The pairs are ordered by i ascending, then by j ascending: for the t-th match of row i at pair position p,
+ *     out_left[p] = i and out_right[p] = right_perm[start[i] + t].  With RSX_JOIN_LEFT a row without a match yields ONE pair
+ *     (i, all ones): -1 in either index width, what pandas.merge(how="left")'s indexer returns.  Pair positions are 64-bit
+ *     throughout.
+ *   - *n_pairs is always set.  Where it exceeds `capacity` (the entries each output has room for) the call returns RSX_EINVAL
+ *     "does not fit" and writes nothing.  Nothing at or past *n_pairs is touched.
+ *   - Either output may be NULL, not both.  count is required where n > 0, start and right_perm where out_right is wanted.
+ *     A position start[i] + t at or past m -- which arrays of phase 1 never name -- reads nothing and yields all ones.
+ *   - Errors: bad idx_bytes or flags, both outputs NULL, a missing input, NULL n_pairs: RSX_EINVAL.  n == 0: RSX_OK, no pairs, no
+ *     device needed; rsx_join_pairs on host pointers counts the pairs on the host and needs no device where there are none or
+ *     they do not fit.  Otherwise, without a GPU: RSX_ENODEVICE, no output written.  A capturing stream: RSX_EINVAL.
+ *   - Blocking, as phase 1.
+ * The expansion costs by its OUTPUT, never by how the pairs are spread over the rows: the rows' pairs are summed by
+ * tiles of RSX_JOIN_ROW_TILE rows and scanned; one workgroup per RSX_JOIN_EXPAND_TILE consecutive pairs finds its first row tile
+ * by binary search, scans that tile's counts in LDS, and every thread finds the row of its pair positions by a search of that
+ * scan.  No atomics, no look-back chain, no spin-wait. */
+enum { RSX_JOIN_TRIVIAL = 0,   /* n == 0 or m == 0                                                   */
+       RSX_JOIN_TABLE   = 1,   /* direct addressing into the count table of the right keys' varying bits */
+       RSX_JOIN_SEARCH  = 2,   /* the right side sorted, the left keys searched as they come         */
+       RSX_JOIN_MERGE   = 3 }; /* both sides sorted, the sorted left keys searched                   */
+enum { RSX_JOIN_LEFT = 1 };    /* flags: a left row without a match yields one pair (i, all ones)    */
+enum { RSX_JOIN_ROW_TILE = 1024, RSX_JOIN_EXPAND_TILE = 4096 };   /* the expansion's tiles: rows, pairs */
+
+typedef struct rsx_join_info {
+	uint32_t route;            /* RSX_JOIN_*                                                            */
+	uint32_t key_bytes;
+	uint32_t varying_bits;     /* of the right keys' derived keys (0: not computed)                     */
+	uint32_t left_sorted;      /* 1: the left side was sorted too (MERGE)                               */
+	uint64_t table_bytes;      /* TABLE: the offsets a probe reads (512 KiB; 1 KiB for 1-byte keys)     */
+	rsx_info sort;             /* what the inner sort of the right side reported                        */
+} rsx_join_info;
+
+int rsx_sort_join_device(const void *d_left, size_t n, const void *d_right, size_t m,
+                         rsx_dtype dtype, rsx_order order,
+                         void *d_start, void *d_count, void *d_right_perm, size_t idx_bytes, uint32_t flags,
+                         void *stream, uint64_t *n_pairs, rsx_join_info *info);
+/* host or device pointers for left / right / start / count / right_perm, as rsx_sort_locate (all of the same kind) */
+int rsx_sort_join(const void *left, size_t n, const void *right, size_t m,
+                  rsx_dtype dtype, rsx_order order,
+                  void *start, void *count, void *right_perm, size_t idx_bytes, uint32_t flags,
+                  uint64_t *n_pairs, rsx_join_info *info);
+
+int rsx_join_pairs_device(const void *d_start, const void *d_count, const void *d_right_perm, size_t n, size_t m,
+                          size_t idx_bytes, uint32_t flags, void *d_out_left, void *d_out_right, uint64_t capacity,
+                          void *stream, uint64_t *n_pairs);
+/* host or device pointers for all five arrays (all of the same kind) */
+int rsx_join_pairs(const void *start, const void *count, const void *right_perm, size_t n, size_t m,
+                   size_t idx_bytes, uint32_t flags, void *out_left, void *out_right, uint64_t capacity,
+                   uint64_t *n_pairs);
 
 /* ---- key + payload (struct-of-arrays) ------------------------------------- */
 

@@ -120,6 +120,18 @@ class LocateInfo(C.Structure):
                 ("search_steps", C.c_uint32), ("counter_sets", C.c_uint32), ("sort", Info)]
 
 
+# rsx_join_info.route, rsx_sort_join* / rsx_join_pairs*' flag, the expansion's tiles (rows, pairs: radix_sorting_amd/csrc/rsx_join_shape.hpp)
+JOIN_TRIVIAL, JOIN_TABLE, JOIN_SEARCH, JOIN_MERGE = range(4)
+JOIN_LEFT = 1
+JOIN_ROW_TILE, JOIN_EXPAND_TILE = 1024, 4096
+
+
+class JoinInfo(C.Structure):
+    """rsx_join_info: the route rsx_sort_join* took, what it saw of the right keys and what the inner sort of the right side reported."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("varying_bits", C.c_uint32), ("left_sorted", C.c_uint32),
+                ("table_bytes", C.c_uint64), ("sort", Info)]
+
+
 LEX_MAX_COLS = 16
 
 
@@ -154,6 +166,7 @@ _PREDINFO = C.POINTER(ReduceInfo)
 _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 _PLOCINFO = C.POINTER(LocateInfo)
+_PJINFO = C.POINTER(JoinInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -187,6 +200,10 @@ ABI = [
     ("rsx_sort_nth", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _PNINFO]),
     ("rsx_sort_locate_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PLOCINFO]),
     ("rsx_sort_locate", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PLOCINFO]),
+    ("rsx_sort_join_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PU64, _PJINFO]),
+    ("rsx_sort_join", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PU64, _PJINFO]),
+    ("rsx_join_pairs_device", _I, [_VP, _VP, _VP, _SZ, _SZ, _SZ, _U32, _VP, _VP, C.c_uint64, _VP, _PU64]),
+    ("rsx_join_pairs", _I, [_VP, _VP, _VP, _SZ, _SZ, _SZ, _U32, _VP, _VP, C.c_uint64, _PU64]),
     ("rsx_sort_lex_device", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _VP, _PLINFO]),
     ("rsx_sort_lex", _I, [_PLCOL, _SZ, _SZ, _VP, _SZ, _PLINFO]),
     ("rsx_sort_pairs_device", _I, [_VP, _VP, _VP, _VP, _SZ, _I, _SZ, _I, _VP, _PINFO]),
@@ -589,6 +606,122 @@ def bucketize(src, edges, right=False, dtype=None, order=ASCENDING, idx_dtype=No
     not be sorted.  In the library's order of the keys, as searchsorted().  Returns (bins, info)."""
     info, _, _, bi = radix_sort_locate(src, edges, dtype, order, idx_dtype, less=False, bins=True, below=not right, stream=stream)
     return bi, info
+
+
+def _join_how(how):
+    if how not in ("inner", "left"):
+        raise RsxError("join: how %r is neither 'inner' nor 'left'" % (how,))
+    return JOIN_LEFT if how == "left" else 0
+
+
+def radix_sort_join_ranges(left, right, dtype=None, order=ASCENDING, how="inner", idx_dtype=None, start=True, count=True,
+                           right_perm=True, stream=None):
+    """rsx_sort_join_device, phase 1 of the join alone: one range into the sorted right side per left row.
+
+    Returns (n_pairs, start, count, right_perm, info), None for what was not asked for: the rows of ``right`` that match
+    ``left[i]`` by kdf(key), by BIT PATTERN, are ``right_perm[start[i] : start[i] + count[i]]`` (``start[i]`` is unspecified
+    where ``count[i] == 0``); ``n_pairs`` is the number of pairs ``how`` yields.  ``start`` / ``count`` / ``right_perm``: True
+    allocates the output (n resp. m elements of ``idx_dtype``, default torch.int32), False leaves it out, a device tensor with
+    room for them is written in place; none at all is legal (the number of pairs alone).  Neither input is written."""
+    import torch
+    flags = _join_how(how)
+    _check_dev(left, right)
+    code = _torch_dtype_code(left) if dtype is None else dtype
+    if left.element_size() != DTYPE_SIZE[code] or right.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("left and right do not match the key type")
+    n, m = left.numel(), right.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+
+    def buf(want, size, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(size, dtype=idx_dtype, device=left.device)
+        _check_dev(want)
+        if want.numel() < size or want.element_size() != idx_bytes:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    st, ct, pm = buf(start, n, "start"), buf(count, n, "count"), buf(right_perm, m, "right_perm")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    info, pairs = JoinInfo(), C.c_uint64(0)
+    check(lib().rsx_sort_join_device(left.data_ptr(), n, right.data_ptr(), m, code, order, ptr(st), ptr(ct), ptr(pm), idx_bytes, flags,
+                                     _stream_ptr(stream), C.byref(pairs), C.byref(info)))
+    cut = lambda t, size: None if t is None else t[:size]
+    return int(pairs.value), cut(st, n), cut(ct, n), cut(pm, m), info
+
+
+def radix_sort_join_pairs(start, count, right_perm, how="inner", left_idx=True, right_idx=True, n_pairs=None, stream=None):
+    """rsx_join_pairs_device, phase 2 of the join alone: the ranges of radix_sort_join_ranges expanded into the pairs
+    (left_idx[p], right_idx[p]), ordered by left row, then by right row; ``how="left"``: a left row without a match yields one
+    pair whose right index is -1.  ``left_idx`` / ``right_idx``: True allocates exactly the number of pairs (``n_pairs`` as phase 1
+    returned it; None: the library counts them first), False leaves the output out (not both), a device tensor is written in
+    place and must have room for the pairs.  Returns (left_idx, right_idx, n_pairs)."""
+    import torch
+    flags = _join_how(how)
+    _check_dev(start, count, right_perm)
+    n, m = count.numel(), right_perm.numel()
+    idx_bytes = count.element_size()
+    if start.element_size() != idx_bytes or right_perm.element_size() != idx_bytes or start.numel() < n:
+        raise RsxError("start, count and right_perm must be of one index type, start as long as count")
+    pairs = C.c_uint64(0)
+
+    def run(lo, ro, capacity):
+        ptr = lambda t: None if t is None else t.data_ptr()
+        return lib().rsx_join_pairs_device(start.data_ptr(), count.data_ptr(), right_perm.data_ptr(), n, m, idx_bytes, flags, ptr(lo), ptr(ro),
+                                           capacity, _stream_ptr(stream), C.byref(pairs))
+
+    if n_pairs is None and (left_idx is True or right_idx is True):
+        # a call without room: it writes nothing and says how many pairs there are
+        rc = run(torch.empty(1, dtype=count.dtype, device=count.device), None, 0)
+        if rc != 0 and pairs.value == 0:
+            check(rc)
+        n_pairs = int(pairs.value)
+
+    def buf(want, what):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(n_pairs, dtype=count.dtype, device=count.device)
+        _check_dev(want)
+        if want.element_size() != idx_bytes:
+            raise RsxError("%s must be of the inputs' index type" % what)
+        return want
+
+    lo, ro = buf(left_idx, "left_idx"), buf(right_idx, "right_idx")
+    if n_pairs == 0 and (lo is not None or ro is not None):
+        return lo, ro, 0     # (an empty tensor has no address to hand over)
+    check(run(lo, ro, min([t.numel() for t in (lo, ro) if t is not None] or [0])))
+    total = int(pairs.value)
+    cut = lambda t: None if t is None else t[:total]
+    return cut(lo), cut(ro), total
+
+
+def radix_sort_join(left, right, how="inner", dtype=None, order=ASCENDING, idx_dtype=None, return_ranges=False, ranges=None,
+                    stream=None):
+    """The equi-join of two key columns (``pandas.merge(..., how=how)``'s indexers, SQL ``JOIN ... ON a.k = b.k``): every pair
+    (i, j) with kdf(left[i]) == kdf(right[j]) by BIT PATTERN (-0.0 and +0.0 differ, a NaN matches the NaN of the same bits),
+    ordered by i, then by j.  ``how="left"``: a left row without a match yields one pair (i, -1).
+
+    Returns (left_idx, right_idx, info): phase 1 (rsx_sort_join_device) finds the ranges and the number of pairs, exactly that
+    many are allocated (``idx_dtype``, default torch.int32), phase 2 (rsx_join_pairs_device) writes them.  ``return_ranges=True``
+    appends (start, count, right_perm) to the result; ``ranges=(start, count, right_perm)`` as an earlier call returned them
+    skips phase 1 (``left`` and ``right`` are not looked at and ``info`` is None)."""
+    info, n_pairs = None, None
+    if ranges is None:
+        n_pairs, st, ct, pm, info = radix_sort_join_ranges(left, right, dtype, order, how, idx_dtype, stream=stream)
+    else:
+        st, ct, pm = ranges
+    li, ri, _ = radix_sort_join_pairs(st, ct, pm, how, n_pairs=n_pairs, stream=stream)
+    return (li, ri, info, st, ct, pm) if return_ranges else (li, ri, info)
+
+
+def isin(src, test, dtype=None, order=ASCENDING, stream=None):
+    """``np.isin(src, test)`` / ``torch.isin(src, test)`` on the derived keys, by BIT PATTERN: phase 1 of the join for ``count``
+    alone, then ``> 0``.  Nothing is sorted where at most 16 bits of ``test`` vary.  Returns (mask, info)."""
+    _, _, ct, _, info = radix_sort_join_ranges(src, test, dtype, order, start=False, count=True, right_perm=False, stream=stream)
+    return ct != 0, info
 
 
 def radix_sort_topk(src, k, dtype=None, order=ASCENDING, keys_out=None, idx_out=None, want_idx=True, stream=None):
@@ -1056,6 +1189,29 @@ def radix_sort_locate_host(src, vals, dtype, order=ASCENDING, idx_dtype=None, le
                                 LOCATE_BINS_BELOW if below else 0, C.byref(info)))
     cut = lambda a, count: None if a is None else a[:count]
     return info, cut(le, m), cut(eq, m), cut(bi, n)
+
+
+def radix_sort_join_host(left, right, dtype, order=ASCENDING, how="inner", idx_dtype=None):
+    """rsx_sort_join and rsx_join_pairs on host numpy buffers; returns (left_idx, right_idx, info, start, count, right_perm)
+    (``idx_dtype``: a 4- or 8-byte numpy integer type, default uint32; a missing match under how="left" is all ones)."""
+    import numpy as np
+    left, right = np.ascontiguousarray(left), np.ascontiguousarray(right)
+    if left.itemsize != DTYPE_SIZE[dtype] or right.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("left and right do not match the key type")
+    flags = _join_how(how)
+    n, m = left.size, right.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+    st, ct, pm = np.empty(n, dtype=idx_dtype), np.empty(n, dtype=idx_dtype), np.empty(m, dtype=idx_dtype)
+    info, pairs = JoinInfo(), C.c_uint64(0)
+    check(lib().rsx_sort_join(left.ctypes.data, n, right.ctypes.data, m, dtype, order, st.ctypes.data, ct.ctypes.data, pm.ctypes.data,
+                              idx_dtype.itemsize, flags, C.byref(pairs), C.byref(info)))
+    total = int(pairs.value)
+    li, ri = np.empty(total, dtype=idx_dtype), np.empty(total, dtype=idx_dtype)
+    check(lib().rsx_join_pairs(st.ctypes.data, ct.ctypes.data, pm.ctypes.data, n, m, idx_dtype.itemsize, flags, li.ctypes.data,
+                               ri.ctypes.data, total, C.byref(pairs)))
+    if int(pairs.value) != total:
+        raise RsxError("rsx_join_pairs found %d pairs, rsx_sort_join %d" % (int(pairs.value), total))
+    return li, ri, info, st, ct, pm
 
 
 def radix_sort_lex_host(cols, dtypes, orders=None, idx_dtype=None):

@@ -28,6 +28,7 @@
 #include "rsx_locate.hpp"
 #include "rsx_lex.hpp"
 #include "rsx_reduce.hpp"
+#include "rsx_join.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -579,6 +580,7 @@ void rsx_release_stream(void *stream)
 #include "rsx_locate_api.hpp"    // rsx_sort_locate[_device]
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
 #include "rsx_reduce_api.hpp"    // rsx_sort_reduce[_device]
+#include "rsx_join_api.hpp"      // rsx_sort_join[_device], rsx_join_pairs[_device]
 
 extern "C" {
 

@@ -215,6 +215,11 @@ struct Ctx {
 	DevBuf locout;      // ... rsx_sort_locate on host buffers: the staged values and the staged outputs
 	DevBuf rcells;      // rsx_sort_reduce*: the table of cells [counts][sums][minima][maxima], or a ReducePart per tile of the sorted array
 	DevBuf rout;        // ... rsx_sort_reduce on host buffers: the staged outputs
+	DevBuf jointab;     // rsx_sort_join*: the table route's counts and offsets of the right keys, behind them two sums per workgroup of the probe
+	DevBuf joinkeys;    // ... the merge route: [left keys n][left keys n], a copy of the left keys and the second buffer of its sort
+	DevBuf joinidx;     // ... [indices n] x 4: the left permutation, the second buffer of its sort, start and count in sorted order; or n counts nobody asked for
+	DevBuf jointiles;   // rsx_sort_join*, rsx_join_pairs*: [row tiles + 1] u64: the pairs of every tile of rows, scanned
+	DevBuf joinout;     // ... on host buffers: the staged outputs (rsx_join_pairs: the staged inputs too)
 	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
 	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
 	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
@@ -337,6 +342,11 @@ struct Ctx {
 		locout.release();
 		rcells.release();
 		rout.release();
+		jointab.release();
+		joinkeys.release();
+		joinidx.release();
+		jointiles.release();
+		joinout.release();
 		lexkeys.release();
 		lexidx.release();
 		lexstage.release();

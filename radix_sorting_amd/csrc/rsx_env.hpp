@@ -90,6 +90,8 @@ struct Env {
 	unsigned reduce_lds_bits = REDUCE_LDS_BITS_COMPILED;  // RSX_REDUCE_LDS_BITS=k (0 .. 12): ... and keeps the cells in LDS while at most k do (beyond: in device memory)
 	unsigned reduce_replicas = 0;    // RSX_REDUCE_REPLICAS=k (tests, probe): the cells kernel keeps k copies of the cells in LDS (0: as many as fit, at most 32)
 	unsigned reduce_force = 0;       // RSX_REDUCE_FORCE=2: rsx_sort_reduce* always takes the sort route
+	unsigned join_force = 0;         // RSX_JOIN_FORCE=2: rsx_sort_join* always searches the left keys as they come; =3: always sorts the left side too
+	bool join_no_table = false;      // RSX_JOIN_NO_TABLE=1: rsx_sort_join* never takes the table route
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
 	// What a variable's text means.  An absent variable leaves the member's default initialiser, which load() restores first:
 	// rsx_reload_env() after a test has taken its variable away is back at the default.
@@ -182,6 +184,8 @@ struct Env {
 		number("RSX_REDUCE_LDS_BITS", &reduce_lds_bits, 0, (int)REDUCE_LDS_BITS_COMPILED);
 		within("RSX_REDUCE_REPLICAS", &reduce_replicas, 1, 32);
 		reduce_force = one_or_two("RSX_REDUCE_FORCE");
+		within("RSX_JOIN_FORCE", &join_force, 2, 3);
+		join_no_table = is_one("RSX_JOIN_NO_TABLE");
 		number("RSX_UNIQUE_MAX_BITS", &unique_max_bits, 0, (int)UNIQUE_MAX_BITS_COMPILED);
 		number("RSX_GROUP_MAX_BITS", &group_max_bits, 0, (int)GROUP_MAX_BITS_COMPILED);
 		within("RSX_TWO_LEVEL_MIN_LOG2", &two_level_min_log2, 22, 30);
