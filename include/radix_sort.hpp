@@ -420,6 +420,25 @@ void radix_sort_locate(const T *src, size_t n, const T *vals, size_t m, IdxType 
 		rsx_detail::fail("radix_sort_locate", rc);
 }
 
+// Not in the reference's header (the split radix_sort_locate only describes): the stable multi-way partition of src (not written) by
+// the m values edges[0 .. m-1] (any order, repeats allowed, need not occur in src; not written).  An element falls in part
+// #{ j : edges[j] at or below it } (flags = RSX_PARTITION_BELOW: strictly below it) -- std::upper_bound resp. std::lower_bound
+// of the element among the sorted edges; the parts are listed in ascending order and inside a part the elements keep their
+// input order (std::stable_partition for one edge).  out_keys (room for n; must not overlap src) = the elements in that order,
+// out_idx (room for n) = the input position of each, offsets (room for m + 2, if given): part p is [offsets[p], offsets[p + 1]).
+// out_keys or out_idx may be nullptr, not both.  By bit pattern through basic_kdfs::kdf; RSX_DESCENDING for the complemented
+// order (rsx_sort_partition).
+template <typename IdxType, typename T>
+void radix_sort_partition(const T *src, size_t n, const T *edges, size_t m, T *out_keys, IdxType *out_idx = nullptr, IdxType *offsets = nullptr,
+                          rsx_order order = RSX_ASCENDING, uint32_t flags = 0)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_partition takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_partition: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_partition(src, n, edges, m, rsx_detail::dtype_of<T>(), order, out_keys, out_idx, offsets, sizeof(IdxType), flags, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_partition", rc);
+}
+
 // Not in the reference's header: the equi-join of two key columns, neither of which is written, in two steps (rsx_sort_join,
 // rsx_join_pairs).  radix_sort_join finds, for every row of `left`, its range into the stable sorted order of `right`:
 // right_perm (room for m) = that order, count[i] (room for n) = the rows of right whose derived key equals left[i]'s, and

@@ -79,6 +79,12 @@
  *   workspace); rsx_sort_locate on host buffers also the staged keys, values and outputs.  Freed by rsx_release /
  *   rsx_release_stream, never allocated inside a stream capture (the call refuses a capturing stream).  If an allocation of
  *   the search or table route fails the call takes the sort route.
+ *   rsx_sort_partition*: in the (device, stream) context: a copy of the m edges and the second buffer of its sort; the scatter
+ *   route's table -- up to 255 edges, 256 eight-byte cumulative counts and two rows of 256 eight-byte entries per workgroup (at
+ *   most 256: 1 MiB); the sort route n bins, 2 n indices and 2 m counts on top of what rsx_sort_locate and rsx_sort_rank keep;
+ *   rsx_sort_partition on host buffers also the staged keys, edges and outputs.  Freed by rsx_release / rsx_release_stream, never
+ *   allocated inside a stream capture (the call refuses a capturing stream).  If the allocation of the scatter route's table
+ *   fails the call takes the sort route.
  *   rsx_sort_join*, rsx_join_pairs*: in the (device, stream) context: the table route's counts and offsets of the right keys
  *   (768 KiB) and two sums per workgroup of its probe; what rsx_sort_pairs / rsx_sort keeps for a copy of the right keys (2 m
  *   keys, 2 m indices where right_perm is wanted); the merge route the same for the left side plus 2 n indices; n indices where
@@ -156,6 +162,12 @@
  *                           RSX_LOCATE_MAX_SEARCH_VALUES; tests lower the cut-off with it);
  *   RSX_LOCATE_COUNTER_SETS=k  (tests, probe) the search kernel keeps k sets of its LDS counters, k in 1 .. 32 (default: as many
  *                           as fit, at most 32);
+ *   RSX_PARTITION_FORCE=2   rsx_sort_partition*: always the sort route (tests run both and compare; tools/partition_probe.py times both);
+ *   RSX_PARTITION_MAX_EDGES=k  rsx_sort_partition*: the scatter route while there are at most k distinct edges, k in 1 .. 255
+ *                           (default RSX_PARTITION_DEFAULT_MAX_EDGES = 3, the measured cut-off, DESIGN.md 4q: with more edges the sort
+ *                           route won where only out_idx is asked for; a caller who wants the keys moved gains by raising it);
+ *   RSX_PARTITION_BALLOT_PARTS=k  rsx_sort_partition*: tiles are ranked by one ballot per part while there are at most k parts, k in
+ *                           0 .. 256 (default 7; beyond: per-wave cells in LDS; rsx_partition_info.rank_form says which ran);
  *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
  *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
  *   RSX_REDUCE_MAX_BITS=k   rsx_sort_reduce*: the cells routes while at most k bits of the derived keys vary, k in 0 .. 24 (default 12,
@@ -653,6 +665,71 @@ int rsx_sort_locate(const void *src, size_t n, const void *vals, size_t m,
                     rsx_dtype dtype, rsx_order order,
                     void *less, void *equal, void *bin, size_t idx_bytes, uint32_t flags,
                     rsx_locate_info *info);
+
+/* ---- the split itself: the keys moved into the parts that given splitters cut them into (std::stable_partition for one
+ *      splitter, np.partition / np.argpartition with several kth, pd.cut followed by ordering by bin, the distribution step of a
+ *      sample sort, range partitioning of a table, dispatch of rows to a few destinations) ------------------------------------ */
+
+/* For m edges that need not occur among the n keys: the keys listed part by part, inside a part in their input order.
+ *   - Result: let K(x) be the derived key of x under dtype and order, as everywhere.  The bin of key i is rsx_sort_locate's
+ *     bin[i] = #{ j : K(edges[j]) <= K(src[i]) }; with RSX_PARTITION_BELOW in flags, #{ j : K(edges[j]) < K(src[i]) }.  There are
+ *     m + 1 parts, part p holds the keys with bin p; the result lists the parts in ascending p and inside a part the keys in
+ *     ascending input position (stable).  out_keys[0 .. n): the keys in that order, as raw bit patterns, unchanged.
+ *     out_idx[0 .. n): for every output position the input row it came from -- np.argsort(bin, kind="stable").
+ *     offsets[0 .. m + 2): offsets[j] = #{ i : bin[i] < j }: offsets[0] = 0, offsets[m + 1] = n, part p is
+ *     [offsets[p], offsets[p + 1]).  With sv the sorted edges, offsets[1 .. m] is searchsorted(sorted keys, sv, 'left')
+ *     ('right' with RSX_PARTITION_BELOW).  The edges may come in any order and may repeat: repeated edges give empty parts.
+ *   - Buffers: d_src and d_edges (device memory, of the same dtype) are never written.  out_keys has room for exactly n keys,
+ *     out_idx for n and offsets for m + 2 entries of idx_bytes (4 or 8) each, and nothing past them is touched.  out_keys or
+ *     out_idx may be NULL, not both; offsets may be NULL.  With idx_bytes == 4, n (and m) must fit, or the call fails with
+ *     RSX_EINVAL "does not fit".  out_keys must not overlap src; out_keys == src is RSX_EINVAL.
+ *   - Trivial cases: n == 0: offsets all zero, nothing else written.  m == 0: one part -- the keys copied, out_idx = 0 .. n-1,
+ *     offsets = {0, n}.
+ *   - Errors: bad dtype, order, idx_bytes or flags, both of out_keys and out_idx NULL, src == NULL with n > 0, edges == NULL with
+ *     m > 0: RSX_EINVAL.  Without a GPU: RSX_ENODEVICE, nothing written.  A capturing stream: RSX_EINVAL (the call waits for the
+ *     number of distinct edges).  A failed allocation of the scatter route's table is not an error: the call takes the sort route.
+ *   - Blocking: as rsx_sort_locate_device -- the call may synchronise `stream`; the outputs are valid for work ordered after it
+ *     on `stream`; *info is complete on return.
+ * Routes (rsx_partition_info.route).  The route depends on the number of distinct edges, the switches and whether
+ * the table could be allocated -- never on n.  RSX_PARTITION_SCATTER, every dtype and at most k DISTINCT edges -- k = RSX_PARTITION_DEFAULT_MAX_EDGES
+ * unless the switch RSX_PARTITION_MAX_EDGES raises it, to at most RSX_PARTITION_MAX_EDGES (256 parts): the edges are sorted and reduced as rsx_sort_locate's search route reduces its values; a workgroup
+ * owns a contiguous share of the keys in memory order; one kernel counts every share's keys per part, one workgroup scans the
+ * counts part-major (the start of every part of every share, and the caller's offsets), and one kernel goes through every share
+ * again tile by tile: it searches each key's part once, ranks the tile stably by part inside each wave (rank_form 1: one ballot
+ * per part; 2: per-wave cells in LDS, the lanes of a part found by one ballot per bit of the part number), stages the tile in LDS
+ * in output order and writes it run by run behind per-part cursors in LDS.  Two reads of the keys; no kernel waits for another
+ * workgroup and none adds to device memory atomically.  RSX_PARTITION_SORT, everything else and RSX_PARTITION_FORCE=2:
+ * rsx_sort_locate_device's bins into workspace, their stable rank sort (rsx_sort_rank_device's machinery: its histogram skips the
+ * constant bytes of the bins), a gather of the keys, and the offsets from locate's less / equal over the sorted edges. */
+enum { RSX_PARTITION_TRIVIAL = 0,   /* n == 0 or m == 0                                                    */
+       RSX_PARTITION_SCATTER = 1,   /* count, scan, stable placement by a searched part: two reads of the keys */
+       RSX_PARTITION_SORT    = 2 }; /* locate's bins, their rank sort, a gather                              */
+enum { RSX_PARTITION_BELOW = 1 };        /* flags: a key's part counts the edges strictly below it         */
+enum { RSX_PARTITION_MAX_EDGES = 255 };  /* more DISTINCT edges than this: the sort route, whatever the switch says */
+enum { RSX_PARTITION_DEFAULT_MAX_EDGES = 3 };  /* ... and by default more than this (RSX_PARTITION_MAX_EDGES=k raises it) */
+
+typedef struct rsx_partition_info {
+	uint32_t route;            /* RSX_PARTITION_*                                                          */
+	uint32_t key_bytes;
+	uint32_t input_reads;      /* SCATTER: 2 (kernels that read all n keys of d_src); otherwise 0           */
+	uint32_t distinct_edges;   /* SCATTER: D, the distinct derived keys among edges; SORT: where the count stopped (0: not counted) */
+	uint32_t search_steps;     /* SCATTER: halvings per key behind the start table (0 .. 8)                 */
+	uint32_t rank_form;        /* SCATTER: 1 ballots, 2 per-wave cells in LDS; otherwise 0                  */
+	uint32_t shares;           /* SCATTER: workgroups of the count and of the placement                     */
+	rsx_locate_info locate;    /* SORT: what the inner rsx_sort_locate_device reported                      */
+	rsx_info sort;             /* SORT: what the inner rank sort of the bins reported                       */
+} rsx_partition_info;
+
+int rsx_sort_partition_device(const void *d_src, size_t n, const void *d_edges, size_t m,
+                              rsx_dtype dtype, rsx_order order,
+                              void *d_out_keys, void *d_out_idx, void *d_offsets, size_t idx_bytes, uint32_t flags,
+                              void *stream, rsx_partition_info *info);
+/* host or device pointers for src / edges / out_keys / out_idx / offsets, as rsx_sort_locate (all of the same kind); n == 0 on
+ * host pointers needs no device */
+int rsx_sort_partition(const void *src, size_t n, const void *edges, size_t m,
+                       rsx_dtype dtype, rsx_order order,
+                       void *out_keys, void *out_idx, void *offsets, size_t idx_bytes, uint32_t flags,
+                       rsx_partition_info *info);
 
 /* ---- ordering by several key columns (the stability argument one level up: README.md, "this is only possible because
  *      the sort is stable") ------------------------------------------------------------------------------------------ */

@@ -120,6 +120,23 @@ class LocateInfo(C.Structure):
                 ("search_steps", C.c_uint32), ("counter_sets", C.c_uint32), ("sort", Info)]
 
 
+# rsx_partition_info.route, the scatter route's cut-off, rsx_sort_partition*'s flag
+PARTITION_TRIVIAL, PARTITION_SCATTER, PARTITION_SORT = range(3)
+PARTITION_MAX_EDGES = 255             # the most the scatter route takes (RSX_PARTITION_MAX_EDGES=255)
+PARTITION_DEFAULT_MAX_EDGES = 3       # ... and what it takes by default
+PARTITION_BELOW = 1
+# the placement's tile (keys), the least number of tiles of a workgroup's share and the default of RSX_PARTITION_BALLOT_PARTS
+# (radix_sorting_amd/csrc/rsx_partition_shape.hpp)
+PARTITION_TILE, PARTITION_SHARE_TILES, PARTITION_BALLOT_PARTS = 8192, 2, 7
+
+
+class PartitionInfo(C.Structure):
+    """rsx_partition_info: the route rsx_sort_partition* took, what its search and ranking looked like and what the inner locate and
+    rank sort of the sort route reported."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("input_reads", C.c_uint32), ("distinct_edges", C.c_uint32),
+                ("search_steps", C.c_uint32), ("rank_form", C.c_uint32), ("shares", C.c_uint32), ("locate", LocateInfo), ("sort", Info)]
+
+
 # rsx_join_info.route, rsx_sort_join* / rsx_join_pairs*' flag, the expansion's tiles (rows, pairs: radix_sorting_amd/csrc/rsx_join_shape.hpp)
 JOIN_TRIVIAL, JOIN_TABLE, JOIN_SEARCH, JOIN_MERGE = range(4)
 JOIN_LEFT = 1
@@ -167,6 +184,7 @@ _PNINFO, _PU64 = C.POINTER(NthInfo), C.POINTER(C.c_uint64)
 _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 _PLOCINFO = C.POINTER(LocateInfo)
 _PJINFO = C.POINTER(JoinInfo)
+_PPARTINFO = C.POINTER(PartitionInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -200,6 +218,8 @@ ABI = [
     ("rsx_sort_nth", _I, [_VP, _SZ, _PU64, _SZ, _I, _I, _VP, _VP, _SZ, _PU64, _PU64, _PNINFO]),
     ("rsx_sort_locate_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PLOCINFO]),
     ("rsx_sort_locate", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PLOCINFO]),
+    ("rsx_sort_partition_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PPARTINFO]),
+    ("rsx_sort_partition", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PPARTINFO]),
     ("rsx_sort_join_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PU64, _PJINFO]),
     ("rsx_sort_join", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PU64, _PJINFO]),
     ("rsx_join_pairs_device", _I, [_VP, _VP, _VP, _SZ, _SZ, _SZ, _U32, _VP, _VP, C.c_uint64, _VP, _PU64]),
@@ -606,6 +626,62 @@ def bucketize(src, edges, right=False, dtype=None, order=ASCENDING, idx_dtype=No
     not be sorted.  In the library's order of the keys, as searchsorted().  Returns (bins, info)."""
     info, _, _, bi = radix_sort_locate(src, edges, dtype, order, idx_dtype, less=False, bins=True, below=not right, stream=stream)
     return bi, info
+
+
+def radix_sort_partition(src, edges, dtype=None, order=ASCENDING, idx_dtype=None, keys=True, idx=False, offsets=True, below=False,
+                         stream=None):
+    """rsx_sort_partition_device: the keys of ``src`` listed part by part as the values ``edges`` (any order, repeats allowed, need
+    not occur in ``src``; neither tensor is written) cut them -- key i falls in part ``#{ j : edges[j] <= src[i] }`` (``below=True``:
+    ``<``) in the library's order of the keys, the parts come in ascending order and inside a part the keys keep their input order.
+
+    Returns (info, keys, idx, offsets), None for what was not asked for: ``keys`` the n keys in that order, ``idx`` the input row
+    of every output position (``torch.argsort(bins, stable=True)``), ``offsets`` m + 2 entries -- part p is
+    ``[offsets[p], offsets[p + 1])``.  Each: True allocates the output (``idx_dtype``, default torch.int32, for ``idx`` and
+    ``offsets``), False leaves it out, a device tensor with room for it is written in place; ``keys`` or ``idx`` must be wanted."""
+    import torch
+    _check_dev(src, edges)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code] or edges.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src and edges do not match the key type")
+    n, m = src.numel(), edges.numel()
+    idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+
+    def buf(want, count, what, dt, size):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(count, dtype=dt, device=src.device)
+        _check_dev(want)
+        if want.numel() < count or want.element_size() != size:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    ke = buf(keys, n, "keys", src.dtype, src.element_size())
+    ix, of = buf(idx, n, "idx", idx_dtype, idx_bytes), buf(offsets, m + 2, "offsets", idx_dtype, idx_bytes)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    info = PartitionInfo()
+    check(lib().rsx_sort_partition_device(src.data_ptr(), n, edges.data_ptr(), m, code, order, ptr(ke), ptr(ix), ptr(of), idx_bytes,
+                                          PARTITION_BELOW if below else 0, _stream_ptr(stream), C.byref(info)))
+    cut = lambda t, count: None if t is None else t[:count]
+    return info, cut(ke, n), cut(ix, n), cut(of, m + 2)
+
+
+def partition_even(src, parts, dtype=None, order=ASCENDING, idx_dtype=None, keys=True, idx=False, below=False, stream=None):
+    """``src`` cut into ``parts`` (1 .. 65) parts of as equal size as its ties allow: radix_sort_nth finds the keys at the ranks
+    i * n // parts of the sorted order, radix_sort_partition splits by them.  With ``below=False`` (the default) a key equal to a
+    splitter goes to the part above it, so ``offsets[i]`` is the number of keys below the i-th splitter (nth's ``n_less``):
+    exactly ``i * n // parts`` where the keys are distinct.  Returns (info, keys, idx, offsets, splitters) as radix_sort_partition does, ``offsets`` of parts + 1 entries."""
+    if not 1 <= parts <= NTH_MAX_SELECT_RANKS + 1:
+        raise RsxError("partition_even: parts = %r is not in 1 .. %d" % (parts, NTH_MAX_SELECT_RANKS + 1))
+    n = src.numel()
+    if n == 0:
+        raise RsxError("partition_even: no keys")
+    splitters, _, _, _, _ = radix_sort_nth(src, [i * n // parts for i in range(1, parts)], dtype=dtype, order=order, want_idx=False,
+                                           stream=stream)
+    info, ke, ix, of = radix_sort_partition(src, splitters, dtype, order, idx_dtype, keys=keys, idx=idx, offsets=True, below=below,
+                                            stream=stream)
+    return info, ke, ix, of, splitters
 
 
 def _join_how(how):
@@ -1189,6 +1265,34 @@ def radix_sort_locate_host(src, vals, dtype, order=ASCENDING, idx_dtype=None, le
                                 LOCATE_BINS_BELOW if below else 0, C.byref(info)))
     cut = lambda a, count: None if a is None else a[:count]
     return info, cut(le, m), cut(eq, m), cut(bi, n)
+
+
+def radix_sort_partition_host(src, edges, dtype, order=ASCENDING, idx_dtype=None, keys=True, idx=False, offsets=True, below=False):
+    """rsx_sort_partition on host numpy buffers; returns (info, keys, idx, offsets) as radix_sort_partition does (``idx_dtype``: a
+    4- or 8-byte numpy integer type, default uint32; an output may also be given as a numpy array with room for its elements)."""
+    import numpy as np
+    src, edges = np.ascontiguousarray(src), np.ascontiguousarray(edges)
+    if src.itemsize != DTYPE_SIZE[dtype] or edges.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src and edges do not match the key type")
+    n, m = src.size, edges.size
+    idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+
+    def buf(want, count, what, dt):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(count, dtype=dt)
+        if want.size < count or want.itemsize != np.dtype(dt).itemsize:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    ke, ix, of = buf(keys, n, "keys", src.dtype), buf(idx, n, "idx", idx_dtype), buf(offsets, m + 2, "offsets", idx_dtype)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    info = PartitionInfo()
+    check(lib().rsx_sort_partition(src.ctypes.data, n, edges.ctypes.data, m, dtype, order, ptr(ke), ptr(ix), ptr(of), idx_dtype.itemsize,
+                                   PARTITION_BELOW if below else 0, C.byref(info)))
+    cut = lambda a, count: None if a is None else a[:count]
+    return info, cut(ke, n), cut(ix, n), cut(of, m + 2)
 
 
 def radix_sort_join_host(left, right, dtype, order=ASCENDING, how="inner", idx_dtype=None):

@@ -26,6 +26,7 @@
 #include "rsx_topk.hpp"
 #include "rsx_nth.hpp"
 #include "rsx_locate.hpp"
+#include "rsx_partition.hpp"
 #include "rsx_lex.hpp"
 #include "rsx_reduce.hpp"
 #include "rsx_join.hpp"
@@ -578,6 +579,7 @@ void rsx_release_stream(void *stream)
 #include "rsx_topk_api.hpp"      // rsx_sort_topk[_device]
 #include "rsx_nth_api.hpp"       // rsx_sort_nth[_device]
 #include "rsx_locate_api.hpp"    // rsx_sort_locate[_device]
+#include "rsx_partition_api.hpp" // rsx_sort_partition[_device]
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
 #include "rsx_reduce_api.hpp"    // rsx_sort_reduce[_device]
 #include "rsx_join_api.hpp"      // rsx_sort_join[_device], rsx_join_pairs[_device]

@@ -223,6 +223,10 @@ struct Ctx {
 	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
 	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
 	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
+	DevBuf parttab;     // rsx_sort_partition*: the scatter route's [header][start table][edges][cum][one row of counts per workgroup][one row of starts per workgroup]
+	DevBuf partvals;    // ... [edges m][edges m]: a copy of the edges and the second buffer of its sort
+	DevBuf partidx;     // ... the sort route: [bins n][indices n][indices n][equal m]: locate's bins, the two halves of their rank sort, locate's equal
+	DevBuf partout;     // ... rsx_sort_partition on host buffers: the staged edges and the staged outputs
 	LogCtl *host_logctl = nullptr;   // pinned: the control block as the device left it
 	hipEvent_t log_ev = nullptr;
 	u32 slack1_cap = 0;
@@ -350,6 +354,10 @@ struct Ctx {
 		lexkeys.release();
 		lexidx.release();
 		lexstage.release();
+		parttab.release();
+		partvals.release();
+		partidx.release();
+		partout.release();
 		if (host_logctl)
 			(void)hipHostFree(host_logctl);
 		host_logctl = nullptr;

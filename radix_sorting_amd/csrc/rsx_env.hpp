@@ -25,6 +25,10 @@ enum : unsigned { LOCATE_MAX_VALUES_DEFAULT = 4096 };
 // rsx_sort_reduce*: the widest table of cells the library was compiled for (in LDS, in device memory) and the widest it takes by
 // default -- the LDS cut-off: the cells in device memory lost to the sort route in every measured row
 enum : unsigned { REDUCE_LDS_BITS_COMPILED = 12, REDUCE_MAX_BITS_COMPILED = 24, REDUCE_MAX_BITS_DEFAULT = 12 };
+// rsx_sort_partition*: the scatter route takes at most this many distinct edges by default (the measured cut-off: beyond it the sort
+// route won some row of the probe; the kernels take 255), and ranks by ballots up to this many parts (the shape
+// header's own copy of the second is PARTITION_BALLOT_PARTS_DEFAULT)
+enum : unsigned { PARTITION_MAX_EDGES_COMPILED = 255, PARTITION_MAX_EDGES_DEFAULT = 3, PARTITION_BALLOT_PARTS_ENV_DEFAULT = 7 };
 struct Env {
 	bool host_register = false;      // RSX_HOST_REGISTER=1
 	bool force_table_rank = false;   // RSX_FORCE_TABLE_RANK=1
@@ -93,6 +97,9 @@ struct Env {
 	unsigned join_force = 0;         // RSX_JOIN_FORCE=2: rsx_sort_join* always searches the left keys as they come; =3: always sorts the left side too
 	bool join_no_table = false;      // RSX_JOIN_NO_TABLE=1: rsx_sort_join* never takes the table route
 	unsigned lex_pack_bytes = LEX_PACK_BYTES_DEFAULT;   // RSX_LEX_PACK_BYTES=k (1 .. 8): rsx_sort_lex* packs columns into keys of at most k bytes (1: one sort per column)
+	unsigned partition_force = 0;    // RSX_PARTITION_FORCE=2: rsx_sort_partition* always takes the sort route
+	unsigned partition_max_edges = PARTITION_MAX_EDGES_DEFAULT;     // RSX_PARTITION_MAX_EDGES=k (1 .. 255; default 3): rsx_sort_partition* scatters while there are at most k distinct edges
+	unsigned partition_ballot_parts = PARTITION_BALLOT_PARTS_ENV_DEFAULT;   // RSX_PARTITION_BALLOT_PARTS=k (0 .. 256; default 7): ... and ranks a tile by one ballot per part while there are at most k parts (beyond: per-wave cells in LDS)
 	// What a variable's text means.  An absent variable leaves the member's default initialiser, which load() restores first:
 	// rsx_reload_env() after a test has taken its variable away is back at the default.
 	static bool is_set(const char *name) { return getenv(name) != nullptr; }
@@ -180,6 +187,9 @@ struct Env {
 		within("RSX_LOCATE_MAX_VALUES", &locate_max_values, 1, (int)LOCATE_MAX_VALUES_DEFAULT);
 		within("RSX_LOCATE_COUNTER_SETS", &locate_counter_sets, 1, 32);
 		within("RSX_LEX_PACK_BYTES", &lex_pack_bytes, 1, 8);
+		partition_force = one_or_two("RSX_PARTITION_FORCE");
+		within("RSX_PARTITION_MAX_EDGES", &partition_max_edges, 1, (int)PARTITION_MAX_EDGES_COMPILED);
+		within("RSX_PARTITION_BALLOT_PARTS", &partition_ballot_parts, 0, 256);
 		number("RSX_REDUCE_MAX_BITS", &reduce_max_bits, 0, (int)REDUCE_MAX_BITS_COMPILED);
 		number("RSX_REDUCE_LDS_BITS", &reduce_lds_bits, 0, (int)REDUCE_LDS_BITS_COMPILED);
 		within("RSX_REDUCE_REPLICAS", &reduce_replicas, 1, 32);
