@@ -54,7 +54,10 @@ def want_reduce(grp, vbits, vdt, float_sums=True):
         if float_sums:
             f = as_f64(vbits, vdt)[by_group]
             ends = np.r_[starts[1:], f.size]
-            total = np.array([math.fsum(f[a:b]) for a, b in zip(starts, ends)], dtype=np.float64).view(np.uint64)
+            total = f[starts] + 0.0                   # (a group of one: math.fsum([v]) is 0.0 + v; millions of them cost no loop)
+            many = np.flatnonzero(ends - starts > 1)
+            total[many] = [math.fsum(f[a:b]) for a, b in zip(starts[many], ends[many])]
+            total = total.view(np.uint64)
     else:
         with np.errstate(over="ignore"):
             total = np.add.reduceat(extended(vbits, vdt)[by_group], starts).astype(np.uint64)
