@@ -51,6 +51,7 @@ using namespace rsx;
 #include "rsx_env.hpp"          // the RSX_* switches
 #include "rsx_seg_layout.hpp"   // SegLayout, SlotParts: where the segmented routes' control block and level-1 slots lie
 #include "rsx_ws_layout.hpp"    // WsLayout: where the parts of a caller-owned workspace lie
+#include "rsx_stage.hpp"        // stage_layout: where the arrays of a blocking call on host buffers lie in Ctx::stage
 #include "rsx_ctx.hpp"          // the error convention, DevBuf, Ctx, profiling, get_ctx
 #include "rsx_route_levels.hpp" // MSB passes and leaves behind a histogram: the control block, the leaves, one and two levels
 #include "rsx_route_blind.hpp"  // ... and without one: gates, sizes, blind_enqueue / pairs_blind_enqueue and their blocking sorts

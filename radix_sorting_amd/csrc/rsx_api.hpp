@@ -79,6 +79,9 @@ int idx_args(const char *who, size_t idx_bytes, size_t n, size_t largest)
 }
 inline size_t idx_last(size_t n) { return n ? n - 1 : 0; }
 
+// the grid of a small grid-stride kernel: `per` items to a workgroup, `most` workgroups at most
+inline unsigned small_grid(u64 count, unsigned per, unsigned most) { return (unsigned)std::min<u64>(most, std::max<u64>(1, (count + per - 1) / per)); }
+
 // rsx_sort_topk*, rsx_sort_nth*: keys of one type in, keys and / or their indices out
 int select_args(const char *who, const void *src, size_t n, rsx_dtype dtype, rsx_order order, const void *out_keys, const void *out_idx,
                 size_t idx_bytes)
@@ -90,30 +93,66 @@ int select_args(const char *who, const void *src, size_t n, rsx_dtype dtype, rsx
 	return idx_args(who, idx_bytes, n, idx_last(n));
 }
 
-// ... the host entry point behind its checks.  run(keys, out_keys, out_idx) is the _device entry point: on the caller's buffers where
-// they are the device's; else on the keys staged in recs[0] as rsx_sort_rank stages them, and the `count` results are brought back
-// through `out` = [keys, padded to 16 bytes][indices]
-template <typename F>
-int select_run(Ctx &c, const char *who, DevBuf &out, const void *src, size_t n, size_t kb, size_t count, void *out_keys, void *out_idx,
-               size_t idx_bytes, F run)
+// ---- host staging: what the blocking entry points do around their _device entry point -------------------------------------------
+// is every pointer of `ps` that is there the device's, the host's, or are they mixed?
+enum PtrKind { PTR_HOST, PTR_DEVICE, PTR_MIXED };
+inline PtrKind pointer_kind(const void *const *ps, size_t count)
 {
-	if (is_device_ptr(src)) {
-		if ((out_keys && !is_device_ptr(out_keys)) || (out_idx && !is_device_ptr(out_idx)))
-			return fail(RSX_EINVAL, "%s: src is a device pointer but an output is not", who);
-		RSX_TRY(run(src, out_keys, out_idx));
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		return RSX_OK;
+	bool device = false, host = false;
+	for (size_t i = 0; i < count; ++i)
+		if (ps[i])
+			(is_device_ptr(ps[i]) ? device : host) = true;
+	return device && host ? PTR_MIXED : device ? PTR_DEVICE : PTR_HOST;
+}
+inline int mixed_pointers(const char *who) { return fail(RSX_EINVAL, "%s: host and device pointers in one call", who); }
+
+// one array of a blocking call.  Key columns are staged as rsx_sort_rank stages them, the first in recs[0], a second in recs[1]
+// (the _device routes leave recs[] alone); every other array in a slot of Ctx::stage (rsx_stage.hpp)
+enum StageHome { STAGE_SLOT, STAGE_RECS0, STAGE_RECS1 };
+struct StageRow {
+	const void *ptr;   // the caller's; nullptr: the array is absent
+	size_t up;         // bytes to upload before the call (0: a pure output)
+	size_t room;       // bytes to set aside on the device (0: nothing is read or written there, so whose memory it is does not matter)
+	StageHome home = STAGE_SLOT;
+};
+
+// ... the host entry point behind its checks and shortcuts.  run(d, back) is the _device entry point on d[i] = the caller's own
+// pointers where they are the device's; else on the staged arrays, and back[i] bytes -- what run() says -- are brought back into
+// each output that is there.  The stream is through when the call returns.
+template <size_t N, typename F> int staged_call(Ctx &c, const char *who, const StageRow (&rows)[N], F run)
+{
+	const void *ps[N];
+	size_t bytes[N], off[N], back[N] = {};
+	void *d[N];
+	for (size_t i = 0; i < N; ++i) {
+		ps[i] = rows[i].room ? rows[i].ptr : nullptr;
+		bytes[i] = rows[i].ptr && rows[i].home == STAGE_SLOT ? rows[i].room : STAGE_ABSENT;
+		d[i] = (void *)rows[i].ptr;
 	}
-	const size_t pad = (count * kb + 15) & ~(size_t)15;
-	RSX_TRY(c.recs[0].ensure(n * kb));
-	RSX_TRY(out.ensure(pad + count * idx_bytes));
-	HIP_TRY(hipMemcpyAsync(c.recs[0].p, src, n * kb, hipMemcpyHostToDevice, c.stream));
-	char *dk = (char *)out.p, *di = dk + pad;
-	RSX_TRY(run(c.recs[0].p, out_keys ? dk : nullptr, out_idx ? di : nullptr));
-	if (out_keys)
-		HIP_TRY(hipMemcpyAsync(out_keys, dk, count * kb, hipMemcpyDeviceToHost, c.stream));
-	if (out_idx)
-		HIP_TRY(hipMemcpyAsync(out_idx, di, count * idx_bytes, hipMemcpyDeviceToHost, c.stream));
+	const PtrKind kind = pointer_kind(ps, N);
+	if (kind == PTR_MIXED)
+		return mixed_pointers(who);
+	if (kind == PTR_HOST) {
+		RSX_TRY(c.stage.ensure(stage_layout(bytes, N, off)));
+		for (size_t i = 0; i < N; ++i) {
+			if (!rows[i].ptr)
+				continue;
+			if (rows[i].home == STAGE_SLOT) {
+				d[i] = (char *)c.stage.p + off[i];
+			} else {
+				DevBuf &b = c.recs[rows[i].home == STAGE_RECS1];
+				RSX_TRY(b.ensure(rows[i].room));
+				d[i] = b.p;
+			}
+			if (rows[i].up)
+				HIP_TRY(hipMemcpyAsync(d[i], rows[i].ptr, rows[i].up, hipMemcpyHostToDevice, c.stream));
+		}
+	}
+	RSX_TRY(run(d, back));
+	if (kind == PTR_HOST)
+		for (size_t i = 0; i < N; ++i)
+			if (rows[i].ptr && back[i])
+				HIP_TRY(hipMemcpyAsync((void *)rows[i].ptr, d[i], back[i], hipMemcpyDeviceToHost, c.stream));
 	HIP_TRY(hipStreamSynchronize(c.stream));
 	return RSX_OK;
 }

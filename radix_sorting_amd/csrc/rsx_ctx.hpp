@@ -1,5 +1,5 @@
 // rsx_ctx.hpp: what every host function uses -- the error convention (fail, HIP_TRY, RSX_TRY), DevBuf, the per (device, stream) context
-// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp, rsx_seg_layout.hpp and rsx_ws_layout.hpp, ahead of the routes.
+// Ctx, profiling, the device checks, get_ctx; part of librsx.so's host side, included by rsx.hip behind rsx_env.hpp, rsx_seg_layout.hpp, rsx_ws_layout.hpp and rsx_stage.hpp, ahead of the routes.
 #pragma once
 
 namespace {
@@ -169,7 +169,8 @@ struct Ctx {
 	DevBuf status;      // [ticket u32, pad to 256 B][tiles * 256 status words]
 	DevBuf keys[2];     // key ping-pong for rank sorts / host staging
 	DevBuf vals[2];     // payload ping-pong for host staging / narrow-index rank
-	DevBuf recs[2];     // record gather staging
+	DevBuf recs[2];     // record gather staging; the key columns of a blocking call on host buffers (staged_call)
+	DevBuf stage;       // ... its other arrays, a slot each (rsx_stage.hpp).  One buffer for every entry point: a blocking call holds `mu` and is through before it returns
 	DevBuf tkeys;       // keys extracted from records (rsx_sort_records_tagged*)
 	DevBuf ckeys;       // rank sorts: the keys' varying bits packed together (RSX_COMPACT_BITS)
 	DevBuf joint;       // 2-byte keys: [65536 u32 counts][65537 u64 offsets] of the 16-bit digit (rsx_joint16_kernel)
@@ -199,34 +200,25 @@ struct Ctx {
 	DevBuf ubits;       // rsx_sort_unique*: the bitmap, one bit per packed value (at most 2^RSX_UNIQUE_MAX_BITS / 8 bytes)
 	DevBuf urecs;       // ... [8 u64: sample / totals][UniqueRec per chunk of the bitmap or tile of the sorted array]
 	DevBuf gcells;      // rsx_sort_group*: one GroupCell per word of the bitmap in ubits: the word and the set bits below it
-	DevBuf gout;        // ... rsx_sort_group on host buffers: the staged outputs
 	DevBuf rdtab;       // rsx_sort_rankdata*: [workgroups][256] u64 bases of the place, or [65536 u32 counts][65537 u64 offsets] of the packed varying bits
-	DevBuf rdout;       // ... rsx_sort_rankdata on host buffers: the staged outputs
 	DevBuf tkctl;       // rsx_sort_topk*: [TopkCtl][rows of the input's ranges][rows of the candidates'][their offsets]
 	DevBuf tkpairs;     // ... the k (key, index) pairs and the second buffers of their sort: [keys k][keys k][indices k][indices k]
 	DevBuf tkcand;      // ... the selected bucket's (key, index) candidates: [keys cap][indices cap], cap = n / 8 + 1024
-	DevBuf tkout;       // ... rsx_sort_topk on host buffers: the staged outputs
 	DevBuf nthctl;      // rsx_sort_nth*: [NthCtl][table: 64 buckets x 256 digits u64][counts of the input's ranges u64]
 	DevBuf nthcand;     // ... the active buckets' (key, index) candidates and the second buffers of their sort: [keys cap] x 2 [indices cap] x 2
 	DevBuf nthio;       // ... [ranks m u64][n_less m u64][n_equal m u64][record of each position m u32]
-	DevBuf nthout;      // ... rsx_sort_nth on host buffers: the staged outputs
 	DevBuf loctab;      // rsx_sort_locate*: the search route's [header][start table][edges][cum][column totals][one row of counts per workgroup], or the table route's counts and offsets of keys and values
 	DevBuf locvals;     // ... [values m][values m]: a copy of the values and the second buffer of its sort
-	DevBuf locout;      // ... rsx_sort_locate on host buffers: the staged values and the staged outputs
 	DevBuf rcells;      // rsx_sort_reduce*: the table of cells [counts][sums][minima][maxima], or a ReducePart per tile of the sorted array
-	DevBuf rout;        // ... rsx_sort_reduce on host buffers: the staged outputs
 	DevBuf jointab;     // rsx_sort_join*: the table route's counts and offsets of the right keys, behind them two sums per workgroup of the probe
 	DevBuf joinkeys;    // ... the merge route: [left keys n][left keys n], a copy of the left keys and the second buffer of its sort
 	DevBuf joinidx;     // ... [indices n] x 4: the left permutation, the second buffer of its sort, start and count in sorted order; or n counts nobody asked for
 	DevBuf jointiles;   // rsx_sort_join*, rsx_join_pairs*: [row tiles + 1] u64: the pairs of every tile of rows, scanned
-	DevBuf joinout;     // ... on host buffers: the staged outputs (rsx_join_pairs: the staged inputs too)
 	DevBuf lexkeys;     // rsx_sort_lex*: [keys n][keys n] of the widest packed type: a group's keys and the second buffer of their sort
 	DevBuf lexidx;      // ... [indices n][indices n][indices n]: the permutation found so far and the second buffer of its sort
-	DevBuf lexstage;    // ... rsx_sort_lex on host buffers: the staged columns and the staged result
 	DevBuf parttab;     // rsx_sort_partition*: the scatter route's [header][start table][edges][cum][one row of counts per workgroup][one row of starts per workgroup]
 	DevBuf partvals;    // ... [edges m][edges m]: a copy of the edges and the second buffer of its sort
 	DevBuf partidx;     // ... the sort route: [bins n][indices n][indices n][equal m]: locate's bins, the two halves of their rank sort, locate's equal
-	DevBuf partout;     // ... rsx_sort_partition on host buffers: the staged edges and the staged outputs
 	LogCtl *host_logctl = nullptr;   // pinned: the control block as the device left it
 	hipEvent_t log_ev = nullptr;
 	u32 slack1_cap = 0;
@@ -319,6 +311,7 @@ struct Ctx {
 			vals[i].release();
 			recs[i].release();
 		}
+		stage.release();
 		tkeys.release();
 		ckeys.release();
 		joint.release();
@@ -330,34 +323,25 @@ struct Ctx {
 		ubits.release();
 		urecs.release();
 		gcells.release();
-		gout.release();
 		rdtab.release();
-		rdout.release();
 		tkctl.release();
 		tkpairs.release();
 		tkcand.release();
-		tkout.release();
 		nthctl.release();
 		nthcand.release();
 		nthio.release();
-		nthout.release();
 		loctab.release();
 		locvals.release();
-		locout.release();
 		rcells.release();
-		rout.release();
 		jointab.release();
 		joinkeys.release();
 		joinidx.release();
 		jointiles.release();
-		joinout.release();
 		lexkeys.release();
 		lexidx.release();
-		lexstage.release();
 		parttab.release();
 		partvals.release();
 		partidx.release();
-		partout.release();
 		if (host_logctl)
 			(void)hipHostFree(host_logctl);
 		host_logctl = nullptr;

@@ -190,13 +190,11 @@ int rsx_sort_group(const void *src, size_t n, rsx_dtype dtype, rsx_order order, 
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	// host buffers: the outputs staged in gout as [inverse][counts][first][keys]
-	void *const outs[4] = {out_inverse, out_counts, out_first, out_keys};
-	const size_t esz[4] = {idx_bytes, idx_bytes, idx_bytes, kb};
-	return staged_run(*c, "rsx_sort_group", c->gout, src, n, kb, idx_bytes, outs, esz, n * kb, [&](const void *dsrc, void *const *o, size_t *count) {
-		RSX_TRY(rsx_sort_group_device(dsrc, n, dtype, order, o[0], o[3], o[1], o[2], idx_bytes, nullptr, n_groups, info));
-		count[0] = n;
-		count[1] = count[2] = count[3] = *n_groups;
+	const StageRow rows[5] = {{src, n * kb, n * kb, STAGE_RECS0}, {out_inverse, 0, n * idx_bytes}, {out_keys, 0, n * kb},
+	                          {out_counts, 0, n * idx_bytes}, {out_first, 0, n * idx_bytes}};
+	return staged_call(*c, "rsx_sort_group", rows, [&](void *const *d, size_t *back) {
+		RSX_TRY(rsx_sort_group_device(d[0], n, dtype, order, d[1], d[2], d[3], d[4], idx_bytes, nullptr, n_groups, info));
+		back[1] = n * idx_bytes, back[2] = *n_groups * kb, back[3] = back[4] = *n_groups * idx_bytes;
 		return (int)RSX_OK;
 	});
 }

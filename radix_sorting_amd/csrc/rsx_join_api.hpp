@@ -22,15 +22,13 @@ template <typename IT> struct JoinOut {
 	bool left;        // RSX_JOIN_LEFT
 };
 
-inline unsigned join_small_grid(u64 items, unsigned threads, unsigned most) { return (unsigned)std::min<u64>(most, std::max<u64>(1, (items + threads - 1) / threads)); }
-
 // jointiles = the pairs of every tile of rows, scanned (what the expansion reads); *n_pairs = their total, once the stream is through
 template <typename IT> int join_scan_rows(Ctx &c, const IT *count, size_t n, bool left, u64 *n_pairs)
 {
 	const u64 T = join_tiles(n, JOIN_ROW_TILE);
 	RSX_TRY(c.jointiles.ensure((size_t)(T + 1) * sizeof(u64)));
 	u64 *excl = (u64 *)c.jointiles.p;
-	hipLaunchKernelGGL((rsx_join_rowsums_kernel<IT>), dim3(join_small_grid(T, 1, 65536)), dim3(JOIN_THREADS), 0, c.stream, count, (u64)n, left ? 1u : 0u, excl);
+	hipLaunchKernelGGL((rsx_join_rowsums_kernel<IT>), dim3(small_grid(T, 1, 65536)), dim3(JOIN_THREADS), 0, c.stream, count, (u64)n, left ? 1u : 0u, excl);
 	hipLaunchKernelGGL(rsx_join_scan_kernel, dim3(1), dim3(1024), 0, c.stream, excl, T);
 	HIP_TRY(hipGetLastError());
 	HIP_TRY(hipMemcpyAsync(n_pairs, excl + T, sizeof(u64), hipMemcpyDeviceToHost, c.stream));
@@ -57,7 +55,7 @@ int join_sort_right(Ctx &c, const KT *right, size_t m, int dtype, int order, con
 		if (s.perm)
 			HIP_TRY(hipMemcpyAsync(right_perm, s.perm, m * sizeof(IT), hipMemcpyDeviceToDevice, c.stream));
 		else
-			hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(join_small_grid(m, 256, 1024)), dim3(256), 0, c.stream, right_perm, (u64)m);
+			hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(small_grid(m, 256, 1024)), dim3(256), 0, c.stream, right_perm, (u64)m);
 		HIP_TRY(hipGetLastError());
 		if (!s.perm)
 			info->sort.early_exit = m < 2 ? 1 : 2;
@@ -68,13 +66,7 @@ int join_sort_right(Ctx &c, const KT *right, size_t m, int dtype, int order, con
 		info->sort.early_exit = m < 2 ? 1 : 2;
 		return RSX_OK;
 	}
-	RSX_TRY(c.keys[0].ensure(m * sizeof(KT)));
-	RSX_TRY(c.keys[1].ensure(m * sizeof(KT)));
-	HIP_TRY(hipMemcpyAsync(c.keys[0].p, right, m * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
-	void *res = nullptr;
-	RSX_TRY(sort_keys_device<KT>(c, (KT *)c.keys[0].p, (KT *)c.keys[1].p, m, dtype, order, &res, &info->sort));
-	*sk = (const KT *)res;
-	return RSX_OK;
+	return keybits_keys_sort<KT>(c, right, m, dtype, order, &info->sort, sk);
 }
 
 // route 1: the counts of the right keys' packed varying bits (one-byte keys: of the byte), scanned, and one read of the left keys
@@ -225,16 +217,6 @@ int join_pairs_device(Ctx &c, const IT *start, const IT *count, const IT *perm, 
 	return RSX_OK;
 }
 
-// is every pointer of `ps` that is there the device's (1), the host's (0), or are they mixed (-1)?
-inline int join_pointer_kind(const void *const *ps, size_t count)
-{
-	bool device = false, host = false;
-	for (size_t i = 0; i < count; ++i)
-		if (ps[i])
-			(is_device_ptr(ps[i]) ? device : host) = true;
-	return device && host ? -1 : device ? 1 : 0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -276,9 +258,9 @@ int rsx_sort_join_device(const void *d_left, size_t n, const void *d_right, size
 			HIP_TRY(hipMemsetAsync(d_count, 0, n * idx_bytes, c->stream));
 		if (m && d_right_perm) {
 			if (idx_bytes == 4)
-				hipLaunchKernelGGL((rsx_iota_kernel<u32>), dim3(join_small_grid(m, 256, 1024)), dim3(256), 0, c->stream, (u32 *)d_right_perm, (u64)m);
+				hipLaunchKernelGGL((rsx_iota_kernel<u32>), dim3(small_grid(m, 256, 1024)), dim3(256), 0, c->stream, (u32 *)d_right_perm, (u64)m);
 			else
-				hipLaunchKernelGGL((rsx_iota_kernel<u64>), dim3(join_small_grid(m, 256, 1024)), dim3(256), 0, c->stream, (u64 *)d_right_perm, (u64)m);
+				hipLaunchKernelGGL((rsx_iota_kernel<u64>), dim3(small_grid(m, 256, 1024)), dim3(256), 0, c->stream, (u64 *)d_right_perm, (u64)m);
 			HIP_TRY(hipGetLastError());
 		}
 		HIP_TRY(hipStreamSynchronize(c->stream));
@@ -303,7 +285,7 @@ int rsx_sort_join(const void *left, size_t n, const void *right, size_t m, rsx_d
 	const size_t kb = dtype_size(dtype);
 	RSX_TRY(join_args("rsx_sort_join", left, n, right, m, dtype, order, idx_bytes, flags, n_pairs));
 	const void *const ps[5] = {n ? left : nullptr, m ? right : nullptr, n ? start : nullptr, n ? count : nullptr, m ? right_perm : nullptr};
-	if ((n == 0 || m == 0) && (rsx_device_count() <= 0 || join_pointer_kind(ps, 5) == 0)) {
+	if ((n == 0 || m == 0) && (rsx_device_count() <= 0 || pointer_kind(ps, 5) == PTR_HOST)) {
 		// nothing matches: answered on the host where the buffers are the host's
 		info->route = RSX_JOIN_TRIVIAL;
 		*n_pairs = (flags & RSX_JOIN_LEFT) ? (uint64_t)n : 0;
@@ -317,29 +299,13 @@ int rsx_sort_join(const void *left, size_t n, const void *right, size_t m, rsx_d
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	const int kind = join_pointer_kind(ps, 5);
-	if (kind < 0)
-		return fail(RSX_EINVAL, "rsx_sort_join: host and device pointers in one call");
-	if (kind == 1)
-		return rsx_sort_join_device(left, n, right, m, dtype, order, start, count, right_perm, idx_bytes, flags, nullptr, n_pairs, info);
-	// host buffers: the keys staged in recs[0] and recs[1], joinout = [start][count][right_perm]
-	const size_t npad = idx_slot_bytes(n, idx_bytes), mpad = idx_slot_bytes(m, idx_bytes);
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->recs[1].ensure(m * kb));
-	RSX_TRY(c->joinout.ensure(2 * npad + mpad));
-	char *ds = (char *)c->joinout.p, *dc = ds + npad, *dp = dc + npad;
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, left, n * kb, hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(hipMemcpyAsync(c->recs[1].p, right, m * kb, hipMemcpyHostToDevice, c->stream));
-	RSX_TRY(rsx_sort_join_device(c->recs[0].p, n, c->recs[1].p, m, dtype, order, start ? ds : nullptr, count ? dc : nullptr, right_perm ? dp : nullptr,
-	                             idx_bytes, flags, nullptr, n_pairs, info));
-	if (start)
-		HIP_TRY(hipMemcpyAsync(start, ds, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (count)
-		HIP_TRY(hipMemcpyAsync(count, dc, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (right_perm)
-		HIP_TRY(hipMemcpyAsync(right_perm, dp, m * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	const size_t nb = n * idx_bytes, mb = m * idx_bytes;
+	const StageRow rows[5] = {{left, n * kb, n * kb, STAGE_RECS0}, {right, m * kb, m * kb, STAGE_RECS1}, {start, 0, nb}, {count, 0, nb},
+	                          {right_perm, 0, mb}};
+	return staged_call(*c, "rsx_sort_join", rows, [&](void *const *d, size_t *back) {
+		back[2] = back[3] = nb, back[4] = mb;
+		return rsx_sort_join_device(d[0], n, d[1], m, dtype, order, d[2], d[3], d[4], idx_bytes, flags, nullptr, n_pairs, info);
+	});
 }
 
 /* ---- rsx_join_pairs: matching rows of two key columns, phase 2 (rsx_join.hpp) ---- */
@@ -386,40 +352,30 @@ int rsx_join_pairs(const void *start, const void *count, const void *right_perm,
 	if (n == 0)
 		return RSX_OK;
 	const void *const ps[5] = {start, count, m ? right_perm : nullptr, out_left, out_right};
-	const int kind = rsx_device_count() <= 0 ? 0 : join_pointer_kind(ps, 5);
-	if (kind < 0)
-		return fail(RSX_EINVAL, "rsx_join_pairs: host and device pointers in one call");
-	if (kind == 1)
-		return rsx_join_pairs_device(start, count, right_perm, n, m, idx_bytes, flags, out_left, out_right, capacity, nullptr, n_pairs);
-	// host buffers: the number of pairs is a sum over the caller's own counts
-	const bool left = (flags & RSX_JOIN_LEFT) != 0;
-	u64 pairs = 0;
-	for (size_t i = 0; i < n; ++i)
-		pairs += join_row_pairs(idx_bytes == 4 ? (u64)((const uint32_t *)count)[i] : (u64)((const uint64_t *)count)[i], left);
-	*n_pairs = pairs;
-	if (pairs > capacity)
-		return fail(RSX_EINVAL, "rsx_join_pairs: %llu pairs: the result does not fit a capacity of %llu", (unsigned long long)pairs,
-		            (unsigned long long)capacity);
-	if (pairs == 0)
-		return RSX_OK;
+	const PtrKind kind = rsx_device_count() <= 0 ? PTR_HOST : pointer_kind(ps, 5);
+	if (kind == PTR_MIXED)
+		return mixed_pointers("rsx_join_pairs");
+	u64 pairs = capacity;   // (device buffers: what the caller set aside)
+	if (kind == PTR_HOST) {
+		// the number of pairs is a sum over the caller's own counts
+		const bool left = (flags & RSX_JOIN_LEFT) != 0;
+		pairs = 0;
+		for (size_t i = 0; i < n; ++i)
+			pairs += join_row_pairs(idx_bytes == 4 ? (u64)((const uint32_t *)count)[i] : (u64)((const uint64_t *)count)[i], left);
+		*n_pairs = pairs;
+		if (pairs > capacity)
+			return fail(RSX_EINVAL, "rsx_join_pairs: %llu pairs: the result does not fit a capacity of %llu", (unsigned long long)pairs,
+			            (unsigned long long)capacity);
+		if (pairs == 0)
+			return RSX_OK;
+	}
 	RSX_LOCKED_CTX(c, nullptr);
-	// joinout = [start][count][right_perm][out_left][out_right]
-	const size_t npad = idx_slot_bytes(n, idx_bytes), mpad = idx_slot_bytes(m, idx_bytes), ppad = idx_slot_bytes((size_t)pairs, idx_bytes);
-	RSX_TRY(c->joinout.ensure(2 * npad + mpad + 2 * ppad));
-	char *ds = (char *)c->joinout.p, *dc = ds + npad, *dp = dc + npad, *dl = dp + mpad, *dr = dl + ppad;
-	if (start)
-		HIP_TRY(hipMemcpyAsync(ds, start, n * idx_bytes, hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(hipMemcpyAsync(dc, count, n * idx_bytes, hipMemcpyHostToDevice, c->stream));
-	if (right_perm && m)
-		HIP_TRY(hipMemcpyAsync(dp, right_perm, m * idx_bytes, hipMemcpyHostToDevice, c->stream));
-	RSX_TRY(rsx_join_pairs_device(start ? ds : nullptr, dc, right_perm && m ? dp : nullptr, n, m, idx_bytes, flags, out_left ? dl : nullptr,
-	                              out_right ? dr : nullptr, capacity, nullptr, n_pairs));
-	if (out_left)
-		HIP_TRY(hipMemcpyAsync(out_left, dl, (size_t)pairs * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (out_right)
-		HIP_TRY(hipMemcpyAsync(out_right, dr, (size_t)pairs * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	const size_t nb = n * idx_bytes, mb = m * idx_bytes, pb = (size_t)std::min<u64>(pairs, SIZE_MAX / 8) * idx_bytes;
+	const StageRow rows[5] = {{start, nb, nb}, {count, nb, nb}, {m ? right_perm : nullptr, mb, mb}, {out_left, 0, pb}, {out_right, 0, pb}};
+	return staged_call(*c, "rsx_join_pairs", rows, [&](void *const *d, size_t *back) {
+		back[3] = back[4] = pb;
+		return rsx_join_pairs_device(d[0], d[1], d[2], n, m, idx_bytes, flags, d[3], d[4], capacity, nullptr, n_pairs);
+	});
 }
 
 }  // extern "C"

@@ -1,7 +1,7 @@
 // rsx_keybits_api.hpp: what the host drivers of rsx_sort_unique*, rsx_sort_group* and rsx_sort_rankdata* share -- the front end (a
 // sample of the keys, the plan, the varying bits), the bitmap of the packed values, the heads of a sorted array, the index sort of a
-// workspace copy, single indices, host staging of several outputs (the arithmetic: rsx_keybits.hpp); part of librsx.so's host
-// side, included by rsx.hip behind the routes and rsx_api.hpp, in front of the three drivers.
+// workspace copy and its keys-only counterpart, single indices (the arithmetic: rsx_keybits.hpp); part of librsx.so's host side,
+// included by rsx.hip behind the routes and rsx_api.hpp, in front of the three drivers.
 #pragma once
 
 namespace {
@@ -146,6 +146,18 @@ int keybits_index_sort(Ctx &c, const KT *src, size_t n, int dtype, int order, bo
 	return RSX_OK;
 }
 
+// ... and the keys-only sort of such a copy (keys[0], keys[1]): *sorted = the keys in order (rsx_sort_locate*, rsx_sort_join*)
+template <typename KT> int keybits_keys_sort(Ctx &c, const KT *src, size_t n, int dtype, int order, rsx_info *sort, const KT **sorted)
+{
+	RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
+	RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
+	HIP_TRY(hipMemcpyAsync(c.keys[0].p, src, n * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
+	void *res = nullptr;
+	RSX_TRY(sort_keys_device<KT>(c, (KT *)c.keys[0].p, (KT *)c.keys[1].p, n, dtype, order, &res, sort));
+	*sorted = (const KT *)res;
+	return RSX_OK;
+}
+
 // ---- one index or count of 4 or 8 bytes: on the host; on the device, through with the copy before `v` goes out of scope -------
 inline void put_index(void *p, size_t idx_bytes, u64 v)
 {
@@ -159,39 +171,6 @@ inline int put_index_device(void *d, size_t idx_bytes, u64 v, hipStream_t stream
 	const u32 v32 = (u32)v;
 	HIP_TRY(hipMemcpyAsync(d, idx_bytes == 4 ? (const void *)&v32 : (const void *)&v, idx_bytes, hipMemcpyHostToDevice, stream));
 	HIP_TRY(hipStreamSynchronize(stream));
-	return RSX_OK;
-}
-
-// ---- the host entry point behind its checks, as select_run, for N outputs.  run(keys, outs, count) is the _device entry point: on
-// the caller's buffers where they are the device's; else on the keys staged in recs[0] as rsx_sort_rank stages them and on slots of
-// `buf` (one per output, n indices padded to 256 bytes each, the last one `last_bytes`), and count[i] elements of esz[i] bytes
-// -- what run() says -- are brought back from slot i
-inline size_t idx_slot_bytes(size_t n, size_t idx_bytes) { return (n * idx_bytes + 255) & ~(size_t)255; }
-template <size_t N, typename F>
-int staged_run(Ctx &c, const char *who, DevBuf &buf, const void *src, size_t n, size_t kb, size_t idx_bytes, void *const (&outs)[N],
-               const size_t (&esz)[N], size_t last_bytes, F run)
-{
-	size_t count[N];
-	if (is_device_ptr(src)) {
-		for (void *o : outs)
-			if (o && !is_device_ptr(o))
-				return fail(RSX_EINVAL, "%s: src is a device pointer but an output is not", who);
-		RSX_TRY(run(src, outs, count));
-		HIP_TRY(hipStreamSynchronize(c.stream));
-		return RSX_OK;
-	}
-	const size_t ipad = idx_slot_bytes(n, idx_bytes);
-	RSX_TRY(c.recs[0].ensure(n * kb));
-	RSX_TRY(buf.ensure((N - 1) * ipad + last_bytes));
-	HIP_TRY(hipMemcpyAsync(c.recs[0].p, src, n * kb, hipMemcpyHostToDevice, c.stream));
-	void *dout[N];
-	for (size_t i = 0; i < N; ++i)
-		dout[i] = outs[i] ? (char *)buf.p + i * ipad : nullptr;
-	RSX_TRY(run(c.recs[0].p, dout, count));
-	for (size_t i = 0; i < N; ++i)
-		if (outs[i])
-			HIP_TRY(hipMemcpyAsync(outs[i], dout[i], count[i] * esz[i], hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
 	return RSX_OK;
 }
 

@@ -207,42 +207,40 @@ int rsx_sort_lex(const rsx_lex_col *cols, size_t ncols, size_t n, void *out_idx,
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	const bool dev = is_device_ptr(out_idx);
+	const void *ps[RSX_LEX_MAX_COLS + 1];
 	for (size_t i = 0; i < ncols; ++i)
-		if (is_device_ptr(cols[i].data) != dev)
-			return fail(RSX_EINVAL, "rsx_sort_lex: host and device pointers are mixed (column %zu and the output)", i);
-	if (dev) {
+		ps[i] = cols[i].data;
+	ps[ncols] = out_idx;
+	const PtrKind kind = pointer_kind(ps, ncols + 1);
+	if (kind == PTR_MIXED)
+		return mixed_pointers("rsx_sort_lex");
+	if (kind == PTR_DEVICE) {
 		RSX_TRY(rsx_sort_lex_device(cols, ncols, n, out_idx, idx_bytes, nullptr, info));
 		HIP_TRY(hipStreamSynchronize(c->stream));
 		return RSX_OK;
 	}
-	// host buffers: every DISTINCT column staged once, each on a 256-byte boundary; the n indices brought back
+	// host buffers: every DISTINCT column staged once, a slot each, and one for the n indices, which are brought back
 	rsx_lex_col dcols[RSX_LEX_MAX_COLS];
-	size_t off[RSX_LEX_MAX_COLS], total = 0;
-	bool staged_here[RSX_LEX_MAX_COLS];
+	size_t bytes[RSX_LEX_MAX_COLS + 1], off[RSX_LEX_MAX_COLS + 1], first[RSX_LEX_MAX_COLS];
 	for (size_t i = 0; i < ncols; ++i) {
 		const size_t w = dtype_size((int)cols[i].dtype);
 		size_t j = 0;
 		while (j < i && !(cols[j].data == cols[i].data && dtype_size((int)cols[j].dtype) == w))
 			++j;
-		staged_here[i] = j == i;
-		if (j < i) {
-			off[i] = off[j];
-		} else {
-			off[i] = total;
-			total += (n * w + 255) & ~(size_t)255;
-		}
+		first[i] = j;
+		bytes[i] = j == i ? n * w : STAGE_ABSENT;
 	}
-	RSX_TRY(c->lexstage.ensure(total + n * idx_bytes));
-	char *stage = (char *)c->lexstage.p;
+	bytes[ncols] = n * idx_bytes;
+	RSX_TRY(c->stage.ensure(stage_layout(bytes, ncols + 1, off)));
+	char *stage = (char *)c->stage.p;
 	for (size_t i = 0; i < ncols; ++i) {
 		dcols[i] = cols[i];
-		dcols[i].data = stage + off[i];
-		if (staged_here[i])
-			HIP_TRY(hipMemcpyAsync(stage + off[i], cols[i].data, n * dtype_size((int)cols[i].dtype), hipMemcpyHostToDevice, c->stream));
+		dcols[i].data = stage + off[first[i]];
+		if (first[i] == i)
+			HIP_TRY(hipMemcpyAsync(stage + off[i], cols[i].data, bytes[i], hipMemcpyHostToDevice, c->stream));
 	}
-	RSX_TRY(rsx_sort_lex_device(dcols, ncols, n, stage + total, idx_bytes, nullptr, info));
-	HIP_TRY(hipMemcpyAsync(out_idx, stage + total, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
+	RSX_TRY(rsx_sort_lex_device(dcols, ncols, n, stage + off[ncols], idx_bytes, nullptr, info));
+	HIP_TRY(hipMemcpyAsync(out_idx, stage + off[ncols], n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
 	HIP_TRY(hipStreamSynchronize(c->stream));
 	return RSX_OK;
 }

@@ -16,8 +16,6 @@ template <typename IT> struct LocateOut {
 	bool below;  // RSX_LOCATE_BINS_BELOW
 };
 
-inline unsigned locate_small_grid(u64 count, unsigned threads) { return (unsigned)std::min<u64>(1024, std::max<u64>(1, (count + threads - 1) / threads)); }
-
 // route 2, keys of 1 or 2 bytes: the counts of the derived keys (one byte: the histogram kernel; two: rsx_rankdata_count16_kernel),
 // scanned; less / equal are rsx_rankdata_lookup_kernel over the VALUES in the keys' offsets, the bins the same kernel over the
 // KEYS in the values' offsets (BELOW: its `less`; else the entry behind it).  *done = 0: no room, or too many for 32-bit counts.
@@ -76,13 +74,13 @@ int locate_table(Ctx &c, const KT *src, size_t n, const KT *vals, size_t m, KdfA
 	return RSX_OK;
 }
 
-// the values in sorted order (a workspace copy through the ordinary keys-only sort): locvals = [m values][m values]
-template <typename KT> int locate_sort_values(Ctx &c, const KT *vals, size_t m, int dtype, int order, const KT **sorted)
+// the m values or edges of `src` in sorted order (a workspace copy through the ordinary keys-only sort): buf = [m][m] (locvals; partvals)
+template <typename KT> int sorted_copy(Ctx &c, DevBuf &buf, const KT *src, size_t m, int dtype, int order, const KT **sorted)
 {
 	const size_t mpad = (m + 63) & ~(size_t)63;
-	RSX_TRY(c.locvals.ensure(2 * mpad * sizeof(KT)));
-	KT *v0 = (KT *)c.locvals.p, *v1 = v0 + mpad;
-	HIP_TRY(hipMemcpyAsync(v0, vals, m * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
+	RSX_TRY(buf.ensure(2 * mpad * sizeof(KT)));
+	KT *v0 = (KT *)buf.p, *v1 = v0 + mpad;
+	HIP_TRY(hipMemcpyAsync(v0, src, m * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
 	void *res = v0;
 	if (m >= 2) {
 		rsx_info si;
@@ -103,6 +101,17 @@ struct LocateTab {
 inline size_t locate_tab_bytes(u32 max_d, size_t key_bytes, u32 wgs)
 {
 	return 2048 + (((size_t)max_d * key_bytes + 7) & ~(size_t)7) + ((size_t)max_d + 1) * sizeof(u64) + (size_t)locate_counters(max_d) * sizeof(u64) * ((size_t)wgs + 1);
+}
+// the sorted values `sv` prepared for the search: the distinct ones as edges, their cumulative counts and the start table, and the
+// header that says how many there are -- read back into *h, once the stream is through
+template <typename KT>
+int locate_prepared(Ctx &c, const KT *sv, size_t m, KdfArgs<KT> ka, u32 max_d, void *edges, u64 *cum, u32 *start, LocateHdr *hdr, LocateHdr *h)
+{
+	hipLaunchKernelGGL((rsx_locate_prepare_kernel<KT>), dim3(1), dim3(LOCATE_THREADS), 0, c.stream, sv, (u64)m, ka, max_d, (KT *)edges, cum, start, hdr);
+	HIP_TRY(hipGetLastError());
+	HIP_TRY(hipMemcpyAsync(h, hdr, sizeof *h, hipMemcpyDeviceToHost, c.stream));
+	HIP_TRY(hipStreamSynchronize(c.stream));
+	return RSX_OK;
 }
 inline LocateTab locate_tab(void *p, u32 max_d, size_t key_bytes)
 {
@@ -132,14 +141,10 @@ int locate_search_route(Ctx &c, const KT *src, size_t n, const KT *vals, size_t 
 		if ((out.bin && (u64)m > 0xFFFFFFFFull && sizeof(IT) == 4) || c.loctab.ensure(locate_tab_bytes(max_d, sizeof(KT), g.wgs)) != RSX_OK ||
 		    c.locvals.ensure(2 * ((m + 63) & ~(size_t)63) * sizeof(KT)) != RSX_OK)
 			return RSX_OK;
-		RSX_TRY(locate_sort_values<KT>(c, vals, m, dtype, order, sv));
+		RSX_TRY(sorted_copy<KT>(c, c.locvals, vals, m, dtype, order, sv));
 		const LocateTab t = locate_tab(c.loctab.p, max_d, sizeof(KT));
-		hipLaunchKernelGGL((rsx_locate_prepare_kernel<KT>), dim3(1), dim3(LOCATE_THREADS), 0, c.stream, *sv, (u64)m, ka, max_d, (KT *)t.edges, t.cum,
-		                   t.start, t.hdr);
-		HIP_TRY(hipGetLastError());
 		LocateHdr h;
-		HIP_TRY(hipMemcpyAsync(&h, t.hdr, sizeof h, hipMemcpyDeviceToHost, c.stream));
-		HIP_TRY(hipStreamSynchronize(c.stream));
+		RSX_TRY(locate_prepared<KT>(c, *sv, m, ka, max_d, t.edges, t.cum, t.start, t.hdr, &h));
 		info->distinct_values = h.distinct;
 		if (h.distinct == 0 || h.distinct > max_d)
 			return RSX_OK;
@@ -159,7 +164,7 @@ int locate_search_route(Ctx &c, const KT *src, size_t n, const KT *vals, size_t 
 		HIP_TRY(hipGetLastError());
 		if (out.less || out.equal) {
 			hipLaunchKernelGGL(rsx_locate_colsum_kernel, dim3((ncnt + 63u) / 64u), dim3(1024), 0, c.stream, (const u64 *)t.rows, g.wgs, ncnt, t.tot);
-			hipLaunchKernelGGL((rsx_locate_finish_kernel<KT, IT>), dim3(locate_small_grid(m, 1024)), dim3(1024), 0, c.stream, vals, (u64)m, ka,
+			hipLaunchKernelGGL((rsx_locate_finish_kernel<KT, IT>), dim3(small_grid(m, 1024, 1024)), dim3(1024), 0, c.stream, vals, (u64)m, ka,
 			                   (const KT *)t.edges, h.distinct, (const u64 *)t.tot, out.less, out.equal);
 			HIP_TRY(hipGetLastError());
 		}
@@ -189,30 +194,25 @@ int locate_by_sort(Ctx &c, const KT *src, size_t n, const KT *vals, size_t m, in
 			RSX_TRY(c.urecs.ensure(64));
 			u32 *flag = (u32 *)c.urecs.p;
 			HIP_TRY(hipMemsetAsync(flag, 0, sizeof(u32), c.stream));
-			hipLaunchKernelGGL((rsx_locate_descents_kernel<KT>), dim3(locate_small_grid(n, 256 * 16)), dim3(256), 0, c.stream, src, (u64)n, ka, flag);
+			hipLaunchKernelGGL((rsx_locate_descents_kernel<KT>), dim3(small_grid(n, 256 * 16, 1024)), dim3(256), 0, c.stream, src, (u64)n, ka, flag);
 			HIP_TRY(hipGetLastError());
 			HIP_TRY(hipMemcpyAsync(&descents, flag, sizeof descents, hipMemcpyDeviceToHost, c.stream));
 			HIP_TRY(hipStreamSynchronize(c.stream));
 		}
 		if (descents) {
-			RSX_TRY(c.keys[0].ensure(n * sizeof(KT)));
-			RSX_TRY(c.keys[1].ensure(n * sizeof(KT)));
-			HIP_TRY(hipMemcpyAsync(c.keys[0].p, src, n * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
-			void *res = nullptr;
-			RSX_TRY(sort_keys_device<KT>(c, (KT *)c.keys[0].p, (KT *)c.keys[1].p, n, dtype, order, &res, &info->sort));
-			sk = (const KT *)res;
+			RSX_TRY(keybits_keys_sort<KT>(c, src, n, dtype, order, &info->sort, &sk));
 		} else {
 			info->sort.early_exit = n < 2 ? 1 : 2;
 		}
-		hipLaunchKernelGGL((rsx_locate_sorted_values_kernel<KT, IT>), dim3(locate_small_grid(m, 256)), dim3(256), 0, c.stream, sk, (u64)n, vals, (u64)m,
+		hipLaunchKernelGGL((rsx_locate_sorted_values_kernel<KT, IT>), dim3(small_grid(m, 256, 1024)), dim3(256), 0, c.stream, sk, (u64)n, vals, (u64)m,
 		                   ka, out.less, out.equal);
 		HIP_TRY(hipGetLastError());
 	}
 	if (out.bin) {
 		if (!sv)
-			RSX_TRY(locate_sort_values<KT>(c, vals, m, dtype, order, &sv));
+			RSX_TRY(sorted_copy<KT>(c, c.locvals, vals, m, dtype, order, &sv));
 		const u64 block = ((u64)m + 4095) / 4096;
-		const unsigned grid = locate_small_grid(n, 1024 * 8);
+		const unsigned grid = small_grid(n, 1024 * 8, 1024);
 		if (out.below)
 			hipLaunchKernelGGL((rsx_locate_sorted_bins_kernel<KT, IT, true>), dim3(grid), dim3(1024), 0, c.stream, src, (u64)n, sv, (u64)m, block, ka, out.bin);
 		else
@@ -301,41 +301,12 @@ int rsx_sort_locate(const void *src, size_t n, const void *vals, size_t m, rsx_d
 	if (locate_nothing(n, m, bin))
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, nullptr);
-	const void *const ins[2] = {n ? src : nullptr, m ? vals : nullptr};
-	void *const outs[3] = {m ? less : nullptr, m ? equal : nullptr, n ? bin : nullptr};
-	bool device = false, host = false;
-	for (const void *p : ins)
-		if (p)
-			(is_device_ptr(p) ? device : host) = true;
-	for (void *p : outs)
-		if (p)
-			(is_device_ptr(p) ? device : host) = true;
-	if (device && host)
-		return fail(RSX_EINVAL, "rsx_sort_locate: host and device pointers in one call");
-	if (device) {
-		RSX_TRY(rsx_sort_locate_device(src, n, vals, m, dtype, order, less, equal, bin, idx_bytes, flags, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	// host buffers: the keys staged in recs[0] as rsx_sort_rank stages them, locout = [values][less][equal][bin]
-	const size_t vpad = (m * kb + 255) & ~(size_t)255, mpad = idx_slot_bytes(m, idx_bytes), npad = idx_slot_bytes(n, idx_bytes);
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->locout.ensure(vpad + 2 * mpad + npad));
-	char *dv = (char *)c->locout.p, *dl = dv + vpad, *de = dl + mpad, *db = de + mpad;
-	if (n)
-		HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	if (m)
-		HIP_TRY(hipMemcpyAsync(dv, vals, m * kb, hipMemcpyHostToDevice, c->stream));
-	RSX_TRY(rsx_sort_locate_device(c->recs[0].p, n, dv, m, dtype, order, less ? dl : nullptr, equal ? de : nullptr, bin ? db : nullptr, idx_bytes,
-	                               flags, nullptr, info));
-	if (less && m)
-		HIP_TRY(hipMemcpyAsync(less, dl, m * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (equal && m)
-		HIP_TRY(hipMemcpyAsync(equal, de, m * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (bin && n)
-		HIP_TRY(hipMemcpyAsync(bin, db, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	const size_t mb = m * idx_bytes, nb = n * idx_bytes;
+	const StageRow rows[5] = {{src, n * kb, n * kb, STAGE_RECS0}, {vals, m * kb, m * kb}, {less, 0, mb}, {equal, 0, mb}, {bin, 0, nb}};
+	return staged_call(*c, "rsx_sort_locate", rows, [&](void *const *d, size_t *back) {
+		back[2] = back[3] = mb, back[4] = nb;
+		return rsx_sort_locate_device(d[0], n, d[1], m, dtype, order, d[2], d[3], d[4], idx_bytes, flags, nullptr, info);
+	});
 }
 
 }  // extern "C"

@@ -258,8 +258,10 @@ int rsx_sort_nth(const void *src, size_t n, const uint64_t *ranks, size_t m, rsx
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	return select_run(*c, "rsx_sort_nth", c->nthout, src, n, kb, m, out_keys, out_idx, idx_bytes, [&](const void *dsrc, void *dk, void *di) {
-		return rsx_sort_nth_device(dsrc, n, ranks, m, dtype, order, dk, di, idx_bytes, n_less, n_equal, nullptr, info);
+	const StageRow rows[3] = {{src, n * kb, n * kb, STAGE_RECS0}, {out_keys, 0, m * kb}, {out_idx, 0, m * idx_bytes}};
+	return staged_call(*c, "rsx_sort_nth", rows, [&](void *const *d, size_t *back) {
+		back[1] = m * kb, back[2] = m * idx_bytes;
+		return rsx_sort_nth_device(d[0], n, ranks, m, dtype, order, d[1], d[2], idx_bytes, n_less, n_equal, nullptr, info);
 	});
 }
 

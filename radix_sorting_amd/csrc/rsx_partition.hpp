@@ -12,7 +12,7 @@
 //                                 and kept in a register; the tile is ranked stably by bin, staged in LDS in output order (key,
 //                                 position in the tile, bin) and written run by run behind the workgroup's per-bin cursors in LDS;
 //                                 the keys of the next tile are requested before this one is ranked
-//   rsx_partition_iota_kernel     m == 0: out_idx = 0 .. n-1
+//   (m == 0: out_idx = 0 .. n-1 is rsx_kernels.hpp's rsx_iota_kernel)
 //   rsx_partition_gather_kernel   the sort route: keys and indices through the rank sort of the bins
 //   rsx_partition_ends_kernel     the sort route: offsets[0] = 0, offsets[m + 1] = n, BELOW: offsets[1 + j] += equal[j]
 //
@@ -236,12 +236,6 @@ __global__ __launch_bounds__(1024) void rsx_partition_scan_kernel(const u64 *__r
 	if (offsets)
 		for (u64 j = tid; j < m + 2u; j += 1024u)
 			offsets[j] = (IT)s_excl[partition_offset_entry(s_cum, D, j)];
-}
-
-template <typename IT> __global__ __launch_bounds__(256) void rsx_partition_iota_kernel(IT *__restrict__ out, u64 n)
-{
-	for (u64 i = (u64)blockIdx.x * 256u + threadIdx.x; i < n; i += (u64)gridDim.x * 256u)
-		out[i] = (IT)i;
 }
 
 // out_keys[j] = src[ranks[j]], out_idx[j] = ranks[j]; each may be nullptr (out_idx may BE ranks)

@@ -18,23 +18,6 @@ template <typename KT, typename IT> struct PartitionOut {
 	bool below;    // RSX_PARTITION_BELOW
 };
 
-// the edges in sorted order (a workspace copy through the ordinary keys-only sort): partvals = [m edges][m edges]
-template <typename KT> int partition_sort_edges(Ctx &c, const KT *edges, size_t m, int dtype, int order, const KT **sorted)
-{
-	const size_t mpad = (m + 63) & ~(size_t)63;
-	RSX_TRY(c.partvals.ensure(2 * mpad * sizeof(KT)));
-	KT *v0 = (KT *)c.partvals.p, *v1 = v0 + mpad;
-	HIP_TRY(hipMemcpyAsync(v0, edges, m * sizeof(KT), hipMemcpyDeviceToDevice, c.stream));
-	void *res = v0;
-	if (m >= 2) {
-		rsx_info si;
-		info_clear(&si, dtype);
-		RSX_TRY(sort_keys_device<KT>(c, v0, v1, m, dtype, order, &res, &si));
-	}
-	*sorted = (const KT *)res;
-	return RSX_OK;
-}
-
 // where the parts of the scatter route's table lie in parttab
 struct PartitionTab {
 	LocateHdr *hdr;
@@ -68,12 +51,8 @@ int partition_scatter(Ctx &c, const KT *src, size_t n, const KT *sv, size_t m, i
 	if (c.parttab.ensure(partition_tab_bytes(g.wgs)) != RSX_OK)
 		return RSX_OK;
 	const PartitionTab t = partition_tab(c.parttab.p, g.wgs);
-	hipLaunchKernelGGL((rsx_locate_prepare_kernel<KT>), dim3(1), dim3(LOCATE_THREADS), 0, c.stream, sv, (u64)m, ka, max_d, (KT *)t.edges, t.cum, t.start,
-	                   t.hdr);
-	HIP_TRY(hipGetLastError());
 	LocateHdr h;
-	HIP_TRY(hipMemcpyAsync(&h, t.hdr, sizeof h, hipMemcpyDeviceToHost, c.stream));
-	HIP_TRY(hipStreamSynchronize(c.stream));
+	RSX_TRY(locate_prepared<KT>(c, sv, m, ka, max_d, t.edges, t.cum, t.start, t.hdr, &h));
 	info->distinct_edges = h.distinct;
 	if (h.distinct == 0 || h.distinct > max_d)
 		return RSX_OK;
@@ -103,7 +82,7 @@ int partition_scatter(Ctx &c, const KT *src, size_t n, const KT *sv, size_t m, i
 	return RSX_OK;
 }
 
-inline unsigned partition_small_grid(u64 count) { return (unsigned)std::min<u64>(2048, std::max<u64>(1, (count + 255) / 256)); }
+inline size_t idx_slot_bytes(size_t n, size_t idx_bytes) { return (n * idx_bytes + 255) & ~(size_t)255; }
 
 // route 2: partidx = [bins n][indices n][indices n][less m][equal m]; rsx_sort_locate_device's bins of the keys and less / equal of
 // the sorted edges, the stable rank sort of the bins (their constant bytes cost no pass), keys and indices through it
@@ -123,11 +102,11 @@ int partition_by_sort(Ctx &c, const KT *src, size_t n, const KT *sv, size_t m, i
 		info->distinct_edges = info->locate.distinct_values;
 	void *res = nullptr;
 	RSX_TRY((sort_rank_device<IT, IT>(c, bins, ib, n, unsigned_dtype(sizeof(IT)), RSX_ASCENDING, &res, &info->sort)));
-	hipLaunchKernelGGL((rsx_partition_gather_kernel<KT, IT>), dim3(partition_small_grid(n)), dim3(256), 0, c.stream, src, (const IT *)res, (u64)n,
+	hipLaunchKernelGGL((rsx_partition_gather_kernel<KT, IT>), dim3(small_grid(n, 256, 2048)), dim3(256), 0, c.stream, src, (const IT *)res, (u64)n,
 	                   out.keys, out.idx);
 	if (out.offsets) {
 		HIP_TRY(hipMemcpyAsync(out.offsets + 1, less, m * sizeof(IT), hipMemcpyDeviceToDevice, c.stream));
-		hipLaunchKernelGGL((rsx_partition_ends_kernel<IT>), dim3(partition_small_grid(m + 2)), dim3(256), 0, c.stream, out.offsets,
+		hipLaunchKernelGGL((rsx_partition_ends_kernel<IT>), dim3(small_grid(m + 2, 256, 2048)), dim3(256), 0, c.stream, out.offsets,
 		                   out.below ? (const IT *)equal : (const IT *)nullptr, (u64)m, (u64)n);
 	}
 	HIP_TRY(hipGetLastError());
@@ -140,7 +119,7 @@ int sort_partition_device(Ctx &c, const KT *src, size_t n, const KT *edges, size
                           rsx_partition_info *info)
 {
 	const KT *sv = nullptr;
-	RSX_TRY(partition_sort_edges<KT>(c, edges, m, dtype, order, &sv));
+	RSX_TRY(sorted_copy<KT>(c, c.partvals, edges, m, dtype, order, &sv));   // (sort_locate_device fills locvals while it reads them)
 	if (env().partition_force != 2) {
 		int done = 0;
 		RSX_TRY((partition_scatter<KT, IT>(c, src, n, sv, m, dtype, order, out, info, &done)));
@@ -157,7 +136,7 @@ int partition_one_part(Ctx &c, const void *src, size_t n, size_t kb, void *out_k
 	if (out_keys)
 		HIP_TRY(hipMemcpyAsync(out_keys, src, n * kb, hipMemcpyDeviceToDevice, c.stream));
 	if (out_idx)
-		hipLaunchKernelGGL((rsx_partition_iota_kernel<IT>), dim3(partition_small_grid(n)), dim3(256), 0, c.stream, out_idx, (u64)n);
+		hipLaunchKernelGGL((rsx_iota_kernel<IT>), dim3(small_grid(n, 256, 2048)), dim3(256), 0, c.stream, out_idx, (u64)n);
 	if (offsets)
 		hipLaunchKernelGGL((rsx_partition_ends_kernel<IT>), dim3(1), dim3(256), 0, c.stream, offsets, (const IT *)nullptr, (u64)0, (u64)n);
 	HIP_TRY(hipGetLastError());
@@ -235,37 +214,13 @@ int rsx_sort_partition(const void *src, size_t n, const void *edges, size_t m, r
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	const void *const ptrs[5] = {n ? src : nullptr, m ? edges : nullptr, n ? out_keys : nullptr, n ? out_idx : nullptr, offsets};
-	bool device = false, host = false;
-	for (const void *p : ptrs)
-		if (p)
-			(is_device_ptr(p) ? device : host) = true;
-	if (device && host)
-		return fail(RSX_EINVAL, "rsx_sort_partition: host and device pointers in one call");
-	if (device) {
-		RSX_TRY(rsx_sort_partition_device(src, n, edges, m, dtype, order, out_keys, out_idx, offsets, idx_bytes, flags, nullptr, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	// host buffers: the keys staged in recs[0] as rsx_sort_rank stages them, partout = [edges][keys][indices][offsets]
-	const size_t vpad = (m * kb + 255) & ~(size_t)255, kpad = (n * kb + 255) & ~(size_t)255, npad = idx_slot_bytes(n, idx_bytes),
-	             opad = idx_slot_bytes(m + 2, idx_bytes);
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->partout.ensure(vpad + kpad + npad + opad));
-	char *dv = (char *)c->partout.p, *dk = dv + vpad, *di = dk + kpad, *dof = di + npad;
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, src, n * kb, hipMemcpyHostToDevice, c->stream));
-	if (m)
-		HIP_TRY(hipMemcpyAsync(dv, edges, m * kb, hipMemcpyHostToDevice, c->stream));
-	RSX_TRY(rsx_sort_partition_device(c->recs[0].p, n, dv, m, dtype, order, out_keys ? dk : nullptr, out_idx ? di : nullptr, offsets ? dof : nullptr,
-	                                  idx_bytes, flags, nullptr, info));
-	if (out_keys)
-		HIP_TRY(hipMemcpyAsync(out_keys, dk, n * kb, hipMemcpyDeviceToHost, c->stream));
-	if (out_idx)
-		HIP_TRY(hipMemcpyAsync(out_idx, di, n * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	if (offsets)
-		HIP_TRY(hipMemcpyAsync(offsets, dof, (m + 2) * idx_bytes, hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	const size_t ob = (m + 2) * idx_bytes;
+	const StageRow rows[5] = {{src, n * kb, n * kb, STAGE_RECS0}, {edges, m * kb, m * kb}, {out_keys, 0, n * kb}, {out_idx, 0, n * idx_bytes},
+	                          {offsets, 0, ob}};
+	return staged_call(*c, "rsx_sort_partition", rows, [&](void *const *d, size_t *back) {
+		back[2] = n * kb, back[3] = n * idx_bytes, back[4] = ob;
+		return rsx_sort_partition_device(d[0], n, d[1], m, dtype, order, d[2], d[3], d[4], idx_bytes, flags, nullptr, info);
+	});
 }
 
 }  // extern "C"

@@ -224,14 +224,12 @@ int rsx_sort_rankdata(const void *src, size_t n, rsx_dtype dtype, rsx_order orde
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	// host buffers: the outputs staged in rdout as [place][less][equal]
-	void *const outs[3] = {out_place, out_less, out_equal};
-	const size_t esz[3] = {idx_bytes, idx_bytes, idx_bytes};
-	return staged_run(*c, "rsx_sort_rankdata", c->rdout, src, n, kb, idx_bytes, outs, esz, idx_slot_bytes(n, idx_bytes),
-	                  [&](const void *dsrc, void *const *o, size_t *count) {
-		                  count[0] = count[1] = count[2] = n;
-		                  return rsx_sort_rankdata_device(dsrc, n, dtype, order, o[0], o[1], o[2], idx_bytes, nullptr, info);
-	                  });
+	const StageRow rows[4] = {{src, n * kb, n * kb, STAGE_RECS0}, {out_place, 0, n * idx_bytes}, {out_less, 0, n * idx_bytes},
+	                          {out_equal, 0, n * idx_bytes}};
+	return staged_call(*c, "rsx_sort_rankdata", rows, [&](void *const *d, size_t *back) {
+		back[1] = back[2] = back[3] = n * idx_bytes;
+		return rsx_sort_rankdata_device(d[0], n, dtype, order, d[1], d[2], d[3], idx_bytes, nullptr, info);
+	});
 }
 
 }  // extern "C"

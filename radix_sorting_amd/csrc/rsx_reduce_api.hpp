@@ -273,37 +273,14 @@ int rsx_sort_reduce(const void *keys, const void *vals, size_t n, rsx_dtype dtyp
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	void *const outs[5] = {out_keys, out_counts, out_sum, out_min, out_max};
-	const size_t esz[5] = {kb, idx_bytes, 8, vb, vb};
-	if (is_device_ptr(keys)) {
-		if (!is_device_ptr(vals))
-			return fail(RSX_EINVAL, "rsx_sort_reduce: keys is a device pointer but vals is not");
-		for (void *o : outs)
-			if (o && !is_device_ptr(o))
-				return fail(RSX_EINVAL, "rsx_sort_reduce: keys is a device pointer but an output is not");
-		RSX_TRY(rsx_sort_reduce_device(keys, vals, n, dtype, order, val_dtype, ops, out_keys, out_counts, idx_bytes, out_sum, out_min, out_max, nullptr,
-		                               n_groups, info));
-		HIP_TRY(hipStreamSynchronize(c->stream));
-		return RSX_OK;
-	}
-	// host buffers: the keys staged in recs[0] as rsx_sort_rank stages them, the values beside them in recs[1], the outputs in
-	// five slots of rout (n elements of 8 bytes, padded to 256 bytes, each)
-	const size_t slot = idx_slot_bytes(n, 8);
-	RSX_TRY(c->recs[0].ensure(n * kb));
-	RSX_TRY(c->recs[1].ensure(n * vb));
-	RSX_TRY(c->rout.ensure(5 * slot));
-	HIP_TRY(hipMemcpyAsync(c->recs[0].p, keys, n * kb, hipMemcpyHostToDevice, c->stream));
-	HIP_TRY(hipMemcpyAsync(c->recs[1].p, vals, n * vb, hipMemcpyHostToDevice, c->stream));
-	void *dout[5];
-	for (size_t i = 0; i < 5; ++i)
-		dout[i] = outs[i] ? (char *)c->rout.p + i * slot : nullptr;
-	RSX_TRY(rsx_sort_reduce_device(c->recs[0].p, c->recs[1].p, n, dtype, order, val_dtype, ops, dout[0], dout[1], idx_bytes, dout[2], dout[3], dout[4],
-	                               nullptr, n_groups, info));
-	for (size_t i = 0; i < 5; ++i)
-		if (outs[i])
-			HIP_TRY(hipMemcpyAsync(outs[i], dout[i], *n_groups * esz[i], hipMemcpyDeviceToHost, c->stream));
-	HIP_TRY(hipStreamSynchronize(c->stream));
-	return RSX_OK;
+	// (a sum is 8 bytes wide whatever the values are)
+	const StageRow rows[7] = {{keys, n * kb, n * kb, STAGE_RECS0}, {vals, n * vb, n * vb, STAGE_RECS1}, {out_keys, 0, n * kb},
+	                          {out_counts, 0, n * idx_bytes}, {out_sum, 0, n * 8}, {out_min, 0, n * vb}, {out_max, 0, n * vb}};
+	return staged_call(*c, "rsx_sort_reduce", rows, [&](void *const *d, size_t *back) {
+		RSX_TRY(rsx_sort_reduce_device(d[0], d[1], n, dtype, order, val_dtype, ops, d[2], d[3], idx_bytes, d[4], d[5], d[6], nullptr, n_groups, info));
+		back[2] = *n_groups * kb, back[3] = *n_groups * idx_bytes, back[4] = *n_groups * 8, back[5] = back[6] = *n_groups * vb;
+		return (int)RSX_OK;
+	});
 }
 
 }  // extern "C"

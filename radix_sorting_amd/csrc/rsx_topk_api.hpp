@@ -228,8 +228,10 @@ int rsx_sort_topk(const void *src, size_t n, size_t k, rsx_dtype dtype, rsx_orde
 	if (k == 0)
 		return RSX_OK;
 	RSX_LOCKED_CTX(c, nullptr);
-	return select_run(*c, "rsx_sort_topk", c->tkout, src, n, kb, k, out_keys, out_idx, idx_bytes, [&](const void *dsrc, void *dk, void *di) {
-		return rsx_sort_topk_device(dsrc, n, k, dtype, order, dk, di, idx_bytes, nullptr, info);
+	const StageRow rows[3] = {{src, n * kb, n * kb, STAGE_RECS0}, {out_keys, 0, k * kb}, {out_idx, 0, k * idx_bytes}};
+	return staged_call(*c, "rsx_sort_topk", rows, [&](void *const *d, size_t *back) {
+		back[1] = k * kb, back[2] = k * idx_bytes;
+		return rsx_sort_topk_device(d[0], n, k, dtype, order, d[1], d[2], idx_bytes, nullptr, info);
 	});
 }
 

@@ -163,11 +163,12 @@ int rsx_sort_unique(void *src, void *aux, size_t n, rsx_dtype dtype, rsx_order o
 		return RSX_OK;
 	}
 	RSX_LOCKED_CTX(c, nullptr);
-	if (is_device_ptr(src)) {
-		if (!is_device_ptr(aux) || (counts && !is_device_ptr(counts)))
-			return fail(RSX_EINVAL, "rsx_sort_unique: src is a device pointer but aux or counts is not");
+	const void *const ps[3] = {src, aux, counts};
+	const PtrKind kind = pointer_kind(ps, 3);
+	if (kind == PTR_MIXED)
+		return mixed_pointers("rsx_sort_unique");
+	if (kind == PTR_DEVICE)
 		return rsx_sort_unique_device(src, aux, n, dtype, order, counts, count_bytes, nullptr, result, n_unique, info);
-	}
 	// host buffers: staged as rsx_sort stages them; the distinct keys (and counts) come back into the buffer that
 	// corresponds to the device buffer they ended in, the other one is left as it was
 	RSX_TRY(c->keys[0].ensure(n * kb));

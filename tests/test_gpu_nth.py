@@ -344,7 +344,7 @@ def test_host_entry_point(monkeypatch):
             assert rc == 0, rsa.lib().rsx_last_error()
             nl.check("device pointers, host entry", want, ranks, keys_t, idx_t, n_less, n_equal, info, route)
     rc = rsa.lib().rsx_sort_nth(src_t.data_ptr(), n, r.ctypes.data_as(p64), r.size, rsa.F32, 0, hk.ctypes.data, None, 4, None, None, None)
-    assert rc == -1 and b"src is a device pointer" in rsa.lib().rsx_last_error()
+    assert rc == -1 and b"host and device pointers in one call" in rsa.lib().rsx_last_error()
 
 
 def test_one_key_on_the_device():
