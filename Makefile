@@ -17,7 +17,7 @@ oracle: lib
 	$(MAKE) -C oracle
 
 # C++ checks of the template surface in include/ (they need a GPU to run: tests/test_gpu_cpp.py) ...
-LIB_CHECKS  = dropin_check unique_check group_check rankdata_check topk_check lex_check nth_check locate_check reduce_check join_check partition_check
+LIB_CHECKS  = dropin_check unique_check group_check rankdata_check topk_check lex_check nth_check locate_check reduce_check join_check partition_check threads_check
 # ... and of one pure header of the host side each, tests/cpp/X_check of $(CSRC)/rsx_X.hpp, on the CPU (no GPU, no library:
 # tests/test_env_cpu.py, tests/test_seg_layout_cpu.py, tests/test_ws_layout_cpu.py, tests/test_keybits_cpu.py, tests/test_locate_shape_cpu.py,
 # tests/test_reduce_shape_cpu.py, tests/test_join_shape_cpu.py, tests/test_partition_shape_cpu.py, tests/test_stage_cpu.py)
@@ -27,8 +27,12 @@ CHECKS      = $(addprefix tests/cpp/,$(LIB_CHECKS) $(PURE_CHECKS))
 cpp: $(CHECKS)
 
 $(addprefix tests/cpp/,$(LIB_CHECKS)): tests/cpp/%: tests/cpp/%.cpp include/radix_sort.hpp include/radix_sort_rank.hpp include/radix_sort_basic_kdf.hpp include/rsx.h radix_sorting_amd/librsx.so
-	g++ -std=gnu++17 -O2 -Wall -Iinclude $< -Lradix_sorting_amd -lrsx \
+	g++ -std=gnu++17 -O2 -Wall -Iinclude $(HIP_HOST_CFLAGS) $< -Lradix_sorting_amd -lrsx $(HIP_HOST_LIBS) \
 	-Wl,-rpath,'$$ORIGIN/../../radix_sorting_amd' -Wl,-rpath-link,/opt/rocm/lib -pthread -o $@
+
+# threads_check creates its own streams: the one check that calls the HIP runtime itself (as tools/radix does)
+tests/cpp/threads_check: HIP_HOST_CFLAGS = -I/opt/rocm/include -D__HIP_PLATFORM_AMD__
+tests/cpp/threads_check: HIP_HOST_LIBS = -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib
 
 $(addprefix tests/cpp/,$(PURE_CHECKS)): tests/cpp/%_check: tests/cpp/%_check.cpp $(CSRC)/rsx_%.hpp
 	g++ -std=gnu++17 -O2 -Wall $< -o $@

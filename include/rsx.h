@@ -247,7 +247,8 @@ const char *rsx_version(void);
 size_t      rsx_dtype_size(rsx_dtype dtype);
 /* Bytes of device workspace a sort of n keys of this shape will hold on to. */
 size_t      rsx_workspace_bytes(size_t n, rsx_dtype dtype, size_t payload_bytes);
-/* Release every cached workspace / stream context of the calling process. */
+/* Release every cached workspace / stream context of the calling process.  No other thread may be inside the library
+ * while this runs (the contexts are freed without waiting for their locks). */
 void        rsx_release(void);
 /* One context is kept per (device, stream) the library has been called with; a
  * program that creates many short-lived streams releases them one by one: frees the

@@ -46,6 +46,17 @@ def test_dropin_check_program():
     assert seen == len(golden) == 60
 
 
+def test_threads_check_program():
+    """Four native threads inside the library at once (tests/cpp/threads_check.cpp): three with streams of their own on the
+    device entry points, one on the host-pointer templates; every result against std::sort / std::stable_sort, the last error
+    and the armed histogram per thread, the streams released before they are destroyed."""
+    exe = os.path.join(ROOT, "tests", "cpp", "threads_check")
+    if not os.path.exists(exe):
+        subprocess.run(["make", "-C", ROOT, "cpp"], check=True)
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0 and out.stdout.strip().endswith("threads_check OK"), out.stdout + out.stderr
+
+
 def test_reference_tests_run_unmodified_on_our_headers():
     exe = os.path.join(ROOT, "oracle", "_ref", "radix_tests_dropin")
     if not os.path.exists(exe):
