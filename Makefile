@@ -17,11 +17,11 @@ oracle: lib
 	$(MAKE) -C oracle
 
 # C++ checks of the template surface in include/ (they need a GPU to run: tests/test_gpu_cpp.py) ...
-LIB_CHECKS  = dropin_check unique_check group_check rankdata_check topk_check lex_check nth_check locate_check reduce_check join_check partition_check threads_check
+LIB_CHECKS  = dropin_check unique_check group_check rankdata_check topk_check lex_check nth_check locate_check reduce_check join_check partition_check segments_check threads_check
 # ... and of one pure header of the host side each, tests/cpp/X_check of $(CSRC)/rsx_X.hpp, on the CPU (no GPU, no library:
 # tests/test_env_cpu.py, tests/test_seg_layout_cpu.py, tests/test_ws_layout_cpu.py, tests/test_keybits_cpu.py, tests/test_locate_shape_cpu.py,
-# tests/test_reduce_shape_cpu.py, tests/test_join_shape_cpu.py, tests/test_partition_shape_cpu.py, tests/test_stage_cpu.py)
-PURE_CHECKS = env_check seg_layout_check ws_layout_check stage_check keybits_check locate_shape_check reduce_shape_check join_shape_check partition_shape_check
+# tests/test_reduce_shape_cpu.py, tests/test_join_shape_cpu.py, tests/test_partition_shape_cpu.py, tests/test_segments_shape_cpu.py, tests/test_stage_cpu.py)
+PURE_CHECKS = env_check seg_layout_check ws_layout_check stage_check keybits_check locate_shape_check reduce_shape_check join_shape_check partition_shape_check segments_shape_check
 CHECKS      = $(addprefix tests/cpp/,$(LIB_CHECKS) $(PURE_CHECKS))
 
 cpp: $(CHECKS)

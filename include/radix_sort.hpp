@@ -439,6 +439,24 @@ void radix_sort_partition(const T *src, size_t n, const T *edges, size_t m, T *o
 		rsx_detail::fail("radix_sort_partition", rc);
 }
 
+// Not in the reference's header: many independent arrays sorted in one call.  src (not written) holds m segments, segment s being
+// [offsets[s], offsets[s + 1]) -- m + 1 non-decreasing offsets from 0 to n, not written; offsets == nullptr: m equal rows of n / m
+// elements.  Every segment is sorted on its own, stably: out_keys (room for n; must not overlap src) = the elements, every segment
+// in its own range; out_idx (room for n) = the input position of each, in the whole array or, with local = true, counted from
+// the segment's start.  out_keys or out_idx may be nullptr, not both.  By bit pattern through basic_kdfs::kdf; RSX_DESCENDING for
+// the complemented order (rsx_sort_segments).
+template <typename IdxType, typename T>
+void radix_sort_segments(const T *src, size_t n, const IdxType *offsets, size_t m, T *out_keys, IdxType *out_idx = nullptr,
+                         rsx_order order = RSX_ASCENDING, bool local = false)
+{
+	static_assert(rsx_detail::may_be_default_kdf_v<T, decltype(basic_kdfs::kdf<T>)>, "radix_sort_segments takes the scalar keys basic_kdfs::kdf accepts");
+	static_assert(sizeof(IdxType) == 4 || sizeof(IdxType) == 8, "radix_sort_segments: IdxType of 4 or 8 bytes");
+	const int rc = rsx_sort_segments(src, n, offsets, m, sizeof(IdxType), rsx_detail::dtype_of<T>(), order, out_keys, out_idx,
+	                                 local ? (uint32_t)RSX_SEGMENTS_LOCAL_IDX : 0u, nullptr);
+	if (rc != RSX_OK)
+		rsx_detail::fail("radix_sort_segments", rc);
+}
+
 // Not in the reference's header: the equi-join of two key columns, neither of which is written, in two steps (rsx_sort_join,
 // rsx_join_pairs).  radix_sort_join finds, for every row of `left`, its range into the stable sorted order of `right`:
 // right_perm (room for m) = that order, count[i] (room for n) = the rows of right whose derived key equals left[i]'s, and

@@ -85,6 +85,11 @@
  *   rsx_sort_partition on host buffers also the staged keys, edges and outputs.  Freed by rsx_release / rsx_release_stream, never
  *   allocated inside a stream capture (the call refuses a capturing stream).  If the allocation of the scatter route's table
  *   fails the call takes the sort route.
+ *   rsx_sort_segments*: in the (device, stream) context: the plan -- a record, two rows of eight 8-byte counts per workgroup (at most
+ *   256), 64 KiB for the long segments and m 4-byte segment numbers; the composed route the segment number of every key (n entries
+ *   of 1, 2 or 4 bytes) and n indices on top of what rsx_sort_lex keeps; the long segments' sorts work in rsx_sort_lex's buffers.
+ *   rsx_sort_segments on host buffers also the staged keys, offsets and outputs.  Freed by rsx_release / rsx_release_stream, never
+ *   allocated inside a stream capture (the call refuses a capturing stream).
  *   rsx_sort_join*, rsx_join_pairs*: in the (device, stream) context: the table route's counts and offsets of the right keys
  *   (768 KiB) and two sums per workgroup of its probe; what rsx_sort_pairs / rsx_sort keeps for a copy of the right keys (2 m
  *   keys, 2 m indices where right_perm is wanted); the merge route the same for the left side plus 2 n indices; n indices where
@@ -168,6 +173,11 @@
  *                           route won where only out_idx is asked for; a caller who wants the keys moved gains by raising it);
  *   RSX_PARTITION_BALLOT_PARTS=k  rsx_sort_partition*: tiles are ranked by one ballot per part while there are at most k parts, k in
  *                           0 .. 256 (default 7; beyond: per-wave cells in LDS; rsx_partition_info.rank_form says which ran);
+ *   RSX_SEGMENTS_FORCE=1    rsx_sort_segments*: the LDS route (with long segments: MIXED) wherever it is possible at all, whatever the
+ *                           measured defaults say; =2: always the composed route (tests run all and compare;
+ *                           tools/segments_probe.py times them);
+ *   RSX_SEGMENTS_MAX_LONG=k rsx_sort_segments*: at most k segments too long for LDS are sorted one by one (MIXED), k in 0 .. 4096
+ *                           (default 8, the most with which the host loop still won); more of them: the composed route;
  *   RSX_LEX_PACK_BYTES=k    rsx_sort_lex*: neighbouring columns are packed into keys of at most k bytes, k in 1 .. 8 (default 4;
  *                           1: one sort per column; tests run 1, 4 and 8 and compare, tools/lex_probe.py times them);
  *   RSX_REDUCE_MAX_BITS=k   rsx_sort_reduce*: the cells routes while at most k bits of the derived keys vary, k in 0 .. 24 (default 12,
@@ -780,6 +790,69 @@ int rsx_sort_lex_device(const rsx_lex_col *cols, size_t ncols, size_t n, void *d
                         void *stream, rsx_lex_info *info);
 /* host or device pointers, as rsx_sort (all of the same kind); host columns are staged, each distinct one once */
 int rsx_sort_lex(const rsx_lex_col *cols, size_t ncols, size_t n, void *out_idx, size_t idx_bytes, rsx_lex_info *info);
+
+/* ---- many independent arrays sorted in one call (torch.sort(x, dim=-1) on a [batch, length] tensor, argsort per row, the column
+ *      indices of every row of a CSR matrix, neighbour and candidate lists; rocprim::segmented_radix_sort) ---------------------- */
+
+/* The n keys of src are cut into m segments, CSR style, and every segment is sorted on its own.
+ *   - Segments: d_offsets holds m + 1 entries of idx_bytes (4 or 8); segment s is [offsets[s], offsets[s + 1]).  The offsets must
+ *     not decrease, offsets[0] must be 0 and offsets[m] must be n: anything else is RSX_EINVAL "bad offsets" with no output
+ *     written -- the check runs on the device before anything is written.  d_offsets == NULL means m equal rows of n / m keys;
+ *     then n % m != 0 is RSX_EINVAL.  Empty segments are allowed.
+ *   - Result: let K(x) be the derived key of x under dtype and order, as everywhere.  Inside every segment, independently, the keys
+ *     come out in ascending K, equal K in ascending input position (stable).  out_keys[0 .. n): the raw bit patterns in that
+ *     order; segment s occupies the range it has in the input.  out_idx[0 .. n): the input position each output element came
+ *     from -- the position in the whole array (src[out_idx[j]] == out_keys[j] bit for bit), or with RSX_SEGMENTS_LOCAL_IDX in
+ *     flags the position relative to the segment's start, as torch.sort(dim=-1).indices.  For one segment out_idx is
+ *     rsx_sort_rank_device's result element for element.
+ *   - Buffers: d_src and d_offsets are never written.  out_keys and out_idx have room for exactly n elements (out_idx of idx_bytes
+ *     each) and nothing past them is touched.  Either may be NULL, not both.  out_keys == src or any overlap of the two is
+ *     RSX_EINVAL.  With idx_bytes == 4, n must fit, or the call fails with RSX_EINVAL "does not fit"; m must fit 32 bits always.
+ *   - Trivial cases: n == 0 or m == 0: RSX_OK, route RSX_SEGMENTS_TRIVIAL, nothing written; the host form needs no device.
+ *   - Errors: bad dtype, order, idx_bytes or flags, both outputs NULL, src == NULL with n > 0: RSX_EINVAL.  Without a GPU:
+ *     RSX_ENODEVICE, nothing written.  A capturing stream: RSX_EINVAL (the call waits for its plan).
+ *   - Blocking: as rsx_sort_partition_device -- the call may synchronise `stream`; the outputs are valid for work ordered after it
+ *     on `stream`; *info is complete on return.
+ * Routes (rsx_segments_info.route).  A plan kernel reads the offsets, checks them and lists the segment numbers by
+ * size class (rsx_segments_info.class_count; radix_sorting_amd/csrc/rsx_segments_shape.hpp): 0 lengths 0 and 1, copied; 1 up to
+ * 256 keys, a wave per segment; 2 up to 2048 keys, a workgroup of 256 threads; 3 up to `cap` keys -- what fits the 160 KiB of a
+ * CU's LDS for this key width and these outputs --, a workgroup of 1024 threads; 4 longer than cap.  RSX_SEGMENTS_LDS: no segment is
+ * longer than cap; one launch per class that has segments, in which a team of waves loads a whole segment into LDS, finds which
+ * byte columns vary IN THAT SEGMENT and whether it is in order already, runs one stable LDS-to-LDS pass per varying column and
+ * writes the result: one read and one write of the keys.  RSX_SEGMENTS_MIXED: 1 .. RSX_SEGMENTS_MAX_LONG segments are longer than
+ * cap: those go one by one through the plain sorts on their sub-ranges, the others as before.  RSX_SEGMENTS_LEX: everything
+ * else and RSX_SEGMENTS_FORCE=2: the segment number of every key in the narrowest of u8 / u16 / u32, rsx_sort_lex_device on
+ * (segment, key) and a gather.  Which of the first two is taken BY DEFAULT is a measured choice per size class:
+ * today where every segment is of class 0 or 3 (at most one key, or 2049 .. cap keys) and at most 8 are longer than cap; a call with
+ * a segment of 2 .. 2048 keys takes RSX_SEGMENTS_LEX.  RSX_SEGMENTS_FORCE=1 takes them wherever they are possible at all. */
+enum { RSX_SEGMENTS_TRIVIAL = 0,   /* n == 0 or m == 0                                                         */
+       RSX_SEGMENTS_LDS     = 1,   /* every segment sorted in LDS by a wave or a workgroup                      */
+       RSX_SEGMENTS_MIXED   = 2,   /* ... and the few too long for LDS by the plain sorts, one by one           */
+       RSX_SEGMENTS_LEX     = 3 }; /* rsx_sort_lex_device on (segment number, key), a gather                    */
+enum { RSX_SEGMENTS_LOCAL_IDX = 1 };   /* flags: out_idx counts from the segment's start                        */
+enum { RSX_SEGMENTS_CLASSES = 5 };
+
+typedef struct rsx_segments_info {
+	uint32_t route;            /* RSX_SEGMENTS_*                                                           */
+	uint32_t key_bytes;
+	uint32_t cap;              /* the longest segment the LDS route takes for this dtype and these outputs  */
+	uint32_t pad;
+	uint64_t max_len;          /* the longest segment of the call                                          */
+	uint64_t n_long;           /* segments longer than cap                                                 */
+	uint64_t class_count[RSX_SEGMENTS_CLASSES];   /* segments per size class (above); [4] == n_long        */
+	rsx_lex_info lex;          /* LEX: what the inner rsx_sort_lex_device reported                          */
+	rsx_info sort;             /* MIXED: what the last per-segment sort reported                            */
+} rsx_segments_info;
+
+int rsx_sort_segments_device(const void *d_src, size_t n, const void *d_offsets, size_t m, size_t idx_bytes,
+                             rsx_dtype dtype, rsx_order order,
+                             void *d_out_keys, void *d_out_idx, uint32_t flags,
+                             void *stream, rsx_segments_info *info);
+/* host or device pointers for src / offsets / out_keys / out_idx, as rsx_sort_partition (all of the same kind) */
+int rsx_sort_segments(const void *src, size_t n, const void *offsets, size_t m, size_t idx_bytes,
+                      rsx_dtype dtype, rsx_order order,
+                      void *out_keys, void *out_idx, uint32_t flags,
+                      rsx_segments_info *info);
 
 /* ---- per-group count, sum, min and max of a second column (reduce_by_key over rsx_sort_unique's groups) -------------- */
 

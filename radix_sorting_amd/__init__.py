@@ -172,6 +172,36 @@ class LexInfo(C.Structure):
         return [(int(g.first_col), int(g.ncols), int(g.key_bytes), int(g.sorted_as)) for g in self.group[:self.ngroups]]
 
 
+# rsx_segments_info.route, rsx_sort_segments*'s flag, the size classes and their seams (radix_sorting_amd/csrc/rsx_segments_shape.hpp)
+SEGMENTS_TRIVIAL, SEGMENTS_LDS, SEGMENTS_MIXED, SEGMENTS_LEX = range(4)
+SEGMENTS_LOCAL_IDX = 1
+SEGMENTS_COPY, SEGMENTS_WAVE, SEGMENTS_GROUP, SEGMENTS_BLOCK, SEGMENTS_LONG = range(5)
+SEGMENTS_CLASSES = 5
+SEGMENTS_COPY_MAX, SEGMENTS_WAVE_MAX, SEGMENTS_GROUP_MAX = 1, 256, 2048     # the longest segment of the classes below BLOCK
+SEGMENTS_LDS_BYTES, SEGMENTS_TEAM_FIXED, SEGMENTS_CAP_STEP = 163840, 256, 256
+SEGMENTS_MAX_LONG = 4096              # the most RSX_SEGMENTS_MAX_LONG takes
+SEGMENTS_DEFAULT_MAX_LONG = 8         # ... and its default; the classes (bits) in which the LDS route is the default: BLOCK
+SEGMENTS_DEFAULT_CLASSES = 8
+
+
+def SEGMENTS_CAP(dtype, with_idx):
+    """The longest segment the LDS route takes for keys of ``dtype`` (``with_idx``: out_idx is wanted): rsx_segments_shape.hpp's
+    segments_cap -- a workgroup's 160 KiB less sixteen rows of cells and the exchanged words, over two buffers of keys (and u16
+    positions), in steps of 256, at most 65536."""
+    per = 2 * (DTYPE_SIZE[dtype] + (2 if with_idx else 0))
+    cap = (SEGMENTS_LDS_BYTES - 16 * 1024 - SEGMENTS_TEAM_FIXED) // per // SEGMENTS_CAP_STEP * SEGMENTS_CAP_STEP
+    return min(cap, 65536)
+
+
+class SegmentsInfo(C.Structure):
+    """rsx_segments_info: the route rsx_sort_segments* took, the size classes of its segments and what the inner sorts reported."""
+    _fields_ = [("route", C.c_uint32), ("key_bytes", C.c_uint32), ("cap", C.c_uint32), ("pad", C.c_uint32), ("max_len", C.c_uint64),
+                ("n_long", C.c_uint64), ("class_count", C.c_uint64 * SEGMENTS_CLASSES), ("lex", LexInfo), ("sort", Info)]
+
+    def classes(self):
+        return [int(x) for x in self.class_count]
+
+
 # every symbol include/rsx.h declares: (name, restype, argtypes)
 _VP, _SZ, _I, _U32 = C.c_void_p, C.c_size_t, C.c_int, C.c_uint32
 _PVP, _PINFO = C.POINTER(C.c_void_p), C.POINTER(Info)
@@ -185,6 +215,7 @@ _PLCOL, _PLINFO = C.POINTER(LexCol), C.POINTER(LexInfo)
 _PLOCINFO = C.POINTER(LocateInfo)
 _PJINFO = C.POINTER(JoinInfo)
 _PPARTINFO = C.POINTER(PartitionInfo)
+_PSEGINFO = C.POINTER(SegmentsInfo)
 ABI = [
     ("rsx_device_count", _I, []),
     ("rsx_last_error", C.c_char_p, []),
@@ -220,6 +251,8 @@ ABI = [
     ("rsx_sort_locate", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PLOCINFO]),
     ("rsx_sort_partition_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PPARTINFO]),
     ("rsx_sort_partition", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PPARTINFO]),
+    ("rsx_sort_segments_device", _I, [_VP, _SZ, _VP, _SZ, _SZ, _I, _I, _VP, _VP, _U32, _VP, _PSEGINFO]),
+    ("rsx_sort_segments", _I, [_VP, _SZ, _VP, _SZ, _SZ, _I, _I, _VP, _VP, _U32, _PSEGINFO]),
     ("rsx_sort_join_device", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _VP, _PU64, _PJINFO]),
     ("rsx_sort_join", _I, [_VP, _SZ, _VP, _SZ, _I, _I, _VP, _VP, _VP, _SZ, _U32, _PU64, _PJINFO]),
     ("rsx_join_pairs_device", _I, [_VP, _VP, _VP, _SZ, _SZ, _SZ, _U32, _VP, _VP, C.c_uint64, _VP, _PU64]),
@@ -682,6 +715,73 @@ def partition_even(src, parts, dtype=None, order=ASCENDING, idx_dtype=None, keys
     info, ke, ix, of = radix_sort_partition(src, splitters, dtype, order, idx_dtype, keys=keys, idx=idx, offsets=True, below=below,
                                             stream=stream)
     return info, ke, ix, of, splitters
+
+
+def radix_sort_segments(src, offsets=None, rows=None, dtype=None, order=ASCENDING, idx_dtype=None, keys=True, idx=False, local_idx=False,
+                        stream=None):
+    """rsx_sort_segments_device: the keys of ``src`` cut into segments and every segment sorted on its own, stably, in the library's
+    order of the keys.  ``offsets``: a device tensor of m + 1 non-decreasing entries from 0 to n (4- or 8-byte integers; their width
+    is the width of the indices), segment s is ``[offsets[s], offsets[s + 1])``; or ``rows``: m equal rows of n / m keys.  Neither
+    ``src`` nor ``offsets`` is written.
+
+    Returns (info, keys, idx), None for what was not asked for: ``keys`` the n keys, every segment in its own range, ``idx`` the
+    input position of every output element -- in the whole array, or with ``local_idx`` counted from the segment's start
+    (``torch.sort(dim=-1).indices``).  Each: True allocates the output (``idx_dtype``, default the offsets' type or torch.int32),
+    False leaves it out, a device tensor with room for it is written in place; one of the two must be wanted."""
+    import torch
+    _check_dev(src)
+    code = _torch_dtype_code(src) if dtype is None else dtype
+    if src.element_size() != DTYPE_SIZE[code]:
+        raise RsxError("src does not match the key type")
+    n = src.numel()
+    if (offsets is None) == (rows is None):
+        raise RsxError("radix_sort_segments: give either offsets or rows")
+    if offsets is not None:
+        _check_dev(offsets)
+        if offsets.numel() < 1 or offsets.element_size() not in (4, 8):
+            raise RsxError("offsets must hold m + 1 entries of 4 or 8 bytes")
+        m = offsets.numel() - 1
+        idx_dtype = offsets.dtype if idx_dtype is None else idx_dtype
+    else:
+        m = int(rows)
+        idx_dtype = torch.int32 if idx_dtype is None else idx_dtype
+    idx_bytes = torch.empty(0, dtype=idx_dtype).element_size()
+    if offsets is not None and offsets.element_size() != idx_bytes:
+        raise RsxError("offsets and idx must have elements of the same size")
+
+    def buf(want, what, dt, size):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return torch.empty(n, dtype=dt, device=src.device)
+        _check_dev(want)
+        if want.numel() < n or want.element_size() != size:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    ke, ix = buf(keys, "keys", src.dtype, src.element_size()), buf(idx, "idx", idx_dtype, idx_bytes)
+    ptr = lambda t: None if t is None else t.data_ptr()
+    info = SegmentsInfo()
+    check(lib().rsx_sort_segments_device(src.data_ptr(), n, ptr(offsets), m, idx_bytes, code, order, ptr(ke), ptr(ix),
+                                         SEGMENTS_LOCAL_IDX if local_idx else 0, _stream_ptr(stream), C.byref(info)))
+    cut = lambda t: None if t is None else t[:n]
+    return info, cut(ke), cut(ix)
+
+
+def sort_rows(x, descending=False, stream=None):
+    """``torch.sort(x, dim=-1, descending=descending, stable=True)`` for a contiguous 2-D device tensor, in the library's order of
+    the keys (by bit pattern through the KDF: NaNs have a place, -0.0 stands before +0.0).  Returns (values, indices), indices
+    int64 and local to the row as torch's."""
+    import torch
+    if x.dim() != 2:
+        raise RsxError("sort_rows: a 2-D tensor is expected")
+    rows, cols = x.shape
+    flat = x.contiguous().view(-1)
+    if flat.numel() == 0:
+        return torch.empty_like(x), torch.empty(x.shape, dtype=torch.int64, device=x.device)
+    _, ke, ix = radix_sort_segments(flat, rows=rows, order=DESCENDING if descending else ASCENDING, idx_dtype=torch.int64, keys=True, idx=True,
+                                    local_idx=True, stream=stream)
+    return ke.view(rows, cols), ix.view(rows, cols)
 
 
 def _join_how(how):
@@ -1293,6 +1393,46 @@ def radix_sort_partition_host(src, edges, dtype, order=ASCENDING, idx_dtype=None
                                    PARTITION_BELOW if below else 0, C.byref(info)))
     cut = lambda a, count: None if a is None else a[:count]
     return info, cut(ke, n), cut(ix, n), cut(of, m + 2)
+
+
+def radix_sort_segments_host(src, dtype, offsets=None, rows=None, order=ASCENDING, idx_dtype=None, keys=True, idx=False, local_idx=False):
+    """rsx_sort_segments on host numpy buffers; returns (info, keys, idx) as radix_sort_segments does (``offsets``: a numpy array of
+    m + 1 4- or 8-byte integers, or ``rows``; ``idx_dtype``: default the offsets' type or uint32)."""
+    import numpy as np
+    src = np.ascontiguousarray(src)
+    if src.itemsize != DTYPE_SIZE[dtype]:
+        raise RsxError("src does not match the key type")
+    n = src.size
+    if (offsets is None) == (rows is None):
+        raise RsxError("radix_sort_segments_host: give either offsets or rows")
+    if offsets is not None:
+        offsets = np.ascontiguousarray(offsets)
+        if offsets.size < 1 or offsets.itemsize not in (4, 8):
+            raise RsxError("offsets must hold m + 1 entries of 4 or 8 bytes")
+        m = offsets.size - 1
+        idx_dtype = np.dtype(offsets.dtype if idx_dtype is None else idx_dtype)
+        if idx_dtype.itemsize != offsets.itemsize:
+            raise RsxError("offsets and idx must have elements of the same size")
+    else:
+        m = int(rows)
+        idx_dtype = np.dtype(np.uint32 if idx_dtype is None else idx_dtype)
+
+    def buf(want, what, dt):
+        if want is False or want is None:
+            return None
+        if want is True:
+            return np.empty(n, dtype=dt)
+        if want.size < n or want.itemsize != np.dtype(dt).itemsize:
+            raise RsxError("%s must have room for its elements of the right size" % what)
+        return want
+
+    ke, ix = buf(keys, "keys", src.dtype), buf(idx, "idx", idx_dtype)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    info = SegmentsInfo()
+    check(lib().rsx_sort_segments(src.ctypes.data, n, ptr(offsets), m, idx_dtype.itemsize, dtype, order, ptr(ke), ptr(ix),
+                                  SEGMENTS_LOCAL_IDX if local_idx else 0, C.byref(info)))
+    cut = lambda a: None if a is None else a[:n]
+    return info, cut(ke), cut(ix)
 
 
 def radix_sort_join_host(left, right, dtype, order=ASCENDING, how="inner", idx_dtype=None):

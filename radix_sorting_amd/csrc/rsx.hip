@@ -30,6 +30,7 @@
 #include "rsx_lex.hpp"
 #include "rsx_reduce.hpp"
 #include "rsx_join.hpp"
+#include "rsx_segments.hpp"
 
 #include <hip/hip_runtime.h>
 
@@ -584,6 +585,7 @@ void rsx_release_stream(void *stream)
 #include "rsx_lex_api.hpp"       // rsx_sort_lex[_device]
 #include "rsx_reduce_api.hpp"    // rsx_sort_reduce[_device]
 #include "rsx_join_api.hpp"      // rsx_sort_join[_device], rsx_join_pairs[_device]
+#include "rsx_segments_api.hpp"  // rsx_sort_segments[_device]
 
 extern "C" {
 

@@ -219,6 +219,9 @@ struct Ctx {
 	DevBuf parttab;     // rsx_sort_partition*: the scatter route's [header][start table][edges][cum][one row of counts per workgroup][one row of starts per workgroup]
 	DevBuf partvals;    // ... [edges m][edges m]: a copy of the edges and the second buffer of its sort
 	DevBuf partidx;     // ... the sort route: [bins n][indices n][indices n][equal m]: locate's bins, the two halves of their rank sort, locate's equal
+	DevBuf segtab;      // rsx_sort_segments*: [plan record][one row of counts per workgroup][one row of starts][the long segments' (start, length)][the segment numbers m, class by class]
+	DevBuf segwork;     // ... the composed route: [segment number of every key n][the permutation n] (its sorts work in lex's buffers, as the long segments' sorts do)
+	SegmentsPlan *host_segplan = nullptr, *dev_host_segplan = nullptr;   // pinned, written by rsx_segments_scan_kernel
 	LogCtl *host_logctl = nullptr;   // pinned: the control block as the device left it
 	hipEvent_t log_ev = nullptr;
 	u32 slack1_cap = 0;
@@ -297,6 +300,14 @@ struct Ctx {
 		}
 		return RSX_OK;
 	}
+	int ensure_segplan()
+	{
+		if (!host_segplan) {
+			HIP_TRY(hipHostMalloc((void **)&host_segplan, sizeof(SegmentsPlan), hipHostMallocMapped));
+			HIP_TRY(hipHostGetDevicePointer((void **)&dev_host_segplan, host_segplan, 0));
+		}
+		return RSX_OK;
+	}
 	void release()
 	{
 		if (hstage)
@@ -342,6 +353,11 @@ struct Ctx {
 		parttab.release();
 		partvals.release();
 		partidx.release();
+		segtab.release();
+		segwork.release();
+		if (host_segplan)
+			(void)hipHostFree(host_segplan);
+		host_segplan = dev_host_segplan = nullptr;
 		if (host_logctl)
 			(void)hipHostFree(host_logctl);
 		host_logctl = nullptr;

@@ -29,6 +29,11 @@ enum : unsigned { REDUCE_LDS_BITS_COMPILED = 12, REDUCE_MAX_BITS_COMPILED = 24, 
 // route won some row of the probe; the kernels take 255), and ranks by ballots up to this many parts (the shape
 // header's own copy of the second is PARTITION_BALLOT_PARTS_DEFAULT)
 enum : unsigned { PARTITION_MAX_EDGES_COMPILED = 255, PARTITION_MAX_EDGES_DEFAULT = 3, PARTITION_BALLOT_PARTS_ENV_DEFAULT = 7 };
+// rsx_sort_segments*: the most long segments the host loop of the MIXED route may be asked to take and how many it takes by default
+// (the largest count at which MIXED still beat the baseline on the probe's CSR shape); the size classes (bits 1 << class,
+// rsx_segments_shape.hpp) in which the LDS route is the default: BLOCK, which beat the baseline 6 .. 8x -- WAVE lost with rows of 16 keys
+// and GROUP has no row of its own in the probe; those run under RSX_SEGMENTS_FORCE=1
+enum : unsigned { SEGMENTS_MAX_LONG_COMPILED = 4096, SEGMENTS_MAX_LONG_DEFAULT = 8, SEGMENTS_DEFAULT_CLASSES = 8 };
 struct Env {
 	bool host_register = false;      // RSX_HOST_REGISTER=1
 	bool force_table_rank = false;   // RSX_FORCE_TABLE_RANK=1
@@ -100,6 +105,8 @@ struct Env {
 	unsigned partition_force = 0;    // RSX_PARTITION_FORCE=2: rsx_sort_partition* always takes the sort route
 	unsigned partition_max_edges = PARTITION_MAX_EDGES_DEFAULT;     // RSX_PARTITION_MAX_EDGES=k (1 .. 255; default 3): rsx_sort_partition* scatters while there are at most k distinct edges
 	unsigned partition_ballot_parts = PARTITION_BALLOT_PARTS_ENV_DEFAULT;   // RSX_PARTITION_BALLOT_PARTS=k (0 .. 256; default 7): ... and ranks a tile by one ballot per part while there are at most k parts (beyond: per-wave cells in LDS)
+	unsigned segments_force = 0;     // RSX_SEGMENTS_FORCE=1: rsx_sort_segments* sorts in LDS (and the long segments one by one) wherever that is possible at all; =2: always the composed route
+	unsigned segments_max_long = SEGMENTS_MAX_LONG_DEFAULT;   // RSX_SEGMENTS_MAX_LONG=k (0 .. 4096): ... and takes at most k segments too long for LDS one by one (beyond: the composed route)
 	// What a variable's text means.  An absent variable leaves the member's default initialiser, which load() restores first:
 	// rsx_reload_env() after a test has taken its variable away is back at the default.
 	static bool is_set(const char *name) { return getenv(name) != nullptr; }
@@ -190,6 +197,8 @@ struct Env {
 		partition_force = one_or_two("RSX_PARTITION_FORCE");
 		within("RSX_PARTITION_MAX_EDGES", &partition_max_edges, 1, (int)PARTITION_MAX_EDGES_COMPILED);
 		within("RSX_PARTITION_BALLOT_PARTS", &partition_ballot_parts, 0, 256);
+		segments_force = one_or_two("RSX_SEGMENTS_FORCE");
+		within("RSX_SEGMENTS_MAX_LONG", &segments_max_long, 0, (int)SEGMENTS_MAX_LONG_COMPILED);
 		number("RSX_REDUCE_MAX_BITS", &reduce_max_bits, 0, (int)REDUCE_MAX_BITS_COMPILED);
 		number("RSX_REDUCE_LDS_BITS", &reduce_lds_bits, 0, (int)REDUCE_LDS_BITS_COMPILED);
 		within("RSX_REDUCE_REPLICAS", &reduce_replicas, 1, 32);
